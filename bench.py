@@ -6,6 +6,14 @@ resident in HBM: JSON tokenization (K1), checkpoint page inflate + decode (K2), 
 partition (K3), per-bucket last-writer-wins + retention + compaction + computedState counters
 (K4/K6). `value` = log actions replayed per second over all ranks.
 
+A plain run (`--gpus 1 --steps N --warmup W`) does what that figure needs and no more: it generates
+the table once (cached under --workdir), stages it, warms up, times the N steps, writes the last
+step's outputs with `--dump-outputs DIR` (dump_outputs) and prints the line: metric, value, unit,
+ms_per_step, the workload and the replay's counters. Everything below -- the per-kernel table, the
+roofline and pipelines, the record checksums, the CPU baseline and its parity, the end-to-end and
+export legs, config 4's K5 and checkpoint write -- is measured with `--full` only, whose line holds
+the plain line's keys and these.
+
 Per-kernel truth without taxing the timed steps: an untimed pass (--profile-steps) brackets every
 launch with a HIP event pair on its stream (dr_set_timing; one stream, so the kernels add up to the
 step) and gives `kernels`; the timed steps then carry an event pair around the longest kernel only
@@ -210,6 +218,65 @@ def _pct(xs, q):
     return xs[min(len(xs) - 1, int(q * len(xs)))] if xs else None
 
 
+DUMP_COUNTS = ("num_files", "size_in_bytes", "num_removes", "num_metadata", "num_protocol", "num_set_transactions",
+               "num_actions", "num_file_actions", "version", "malformed_lines")
+DUMP_ROWS = 1 << 18  # rows sampled per side: 5 float64 columns of both sides stay near 25 MB
+DUMP_SEED = 0xD17A
+
+
+def _halves(values):
+    """uint64 values as float64 (high 32 bits, low 32 bits) pairs: exact, where float64 itself is not."""
+    import numpy as np
+    v = np.asarray(values, dtype=np.uint64)
+    return np.stack([(v >> np.uint64(32)).astype(np.float64), (v & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(dirname, st, rows=True):
+    """--dump-outputs: what a caller of the timed path holds after a step -- the replayed state -- as
+    float64 DIR/<name>.npy, the same from run to run of one command (seeded table, fixed row order,
+    fixed sample), so that two builds can be compared array by array:
+      counts            the state's counters, in DUMP_COUNTS order
+      key_sums          live and tombstone order-free key sums, each as (high, low) 32-bit halves
+      record_sums       per side the sum mod 2^64 of every row's full-record hash (every field of every
+                        row of the state), as halves
+    and for each side (live, tombstones) a sample of DUMP_ROWS rows of its export order (all rows of a
+    smaller side), the legacy-seeded numpy generator's draw, sorted:
+      <side>_rows, <side>_size, <side>_path_len, <side>_record_hash (halves), live_modification_time,
+      tombstones_deletion_timestamp (-1 where the remove has none).
+    `rows=False` (a sharded state, whose rows lie on their owners) writes the counters only."""
+    import numpy as np
+    from delta_amd import _native as N
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    c = st.counts
+    save("counts", [c[k] for k in DUMP_COUNTS])
+    save("key_sums", _halves([c["live_key_sum"], c["tomb_key_sum"]]))
+    if not rows:
+        return
+    sums = []
+    for side, which in (("live", N.DR_LIVE), ("tombstones", N.DR_TOMBSTONES)):
+        cols = st.export_columns(which)
+        hashes = st.record_hashes(which)
+        n = len(hashes)
+        sums.append(int(hashes.sum(dtype=np.uint64)))
+        if n > DUMP_ROWS:
+            idx = np.unique(np.random.RandomState(DUMP_SEED).randint(0, n, size=DUMP_ROWS))
+        else:
+            idx = np.arange(n)
+        save(side + "_rows", idx)
+        save(side + "_size", cols["size"][idx] if n else [])
+        save(side + "_path_len", np.diff(cols["path_off"])[idx] if n else [])
+        save(side + "_record_hash", _halves(hashes[idx]))
+        if which == N.DR_LIVE:
+            save("live_modification_time", cols["modification_time"][idx] if n else [])
+        else:
+            dts = np.where(cols["deletion_timestamp_valid"] != 0, cols["deletion_timestamp"], -1) if n else []
+            save("tombstones_deletion_timestamp", dts[idx] if n else [])
+    save("record_sums", _halves(sums))
+
+
 def measure_stream(eng, table, exp, args):
     """Config 5 (BASELINE.json configs[4]): the streaming tail. A full replay of the 50M-file
     checkpoint is the base; the 10k commits that follow (3 adds + 2 removes each) are each staged
@@ -293,11 +360,13 @@ def measure_stream(eng, table, exp, args):
         log("STREAM PARITY MISMATCH (applied, full replay):", mism)
     counts = dict(cur.counts, live_record_sum=rec_cur[0], tomb_record_sum=rec_cur[1])
     full.release()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cur)  # the state the last apply returned
     cur.release()
     base_counts = dict(base.counts)
     base.release()
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(log_path, final_cut, counts, args.cpu_threads, one_core=False, all_cpus=False)
     if cpu:
         # the reference has no incremental path: every DeltaLog.update() rebuilds the snapshot from
@@ -486,7 +555,13 @@ def main():
     ap.add_argument("--driver", choices=("lib", "torch"), default="lib",
                     help="N > 1: the library's own RCCL replay (dr_replay_sharded, what a JNI host calls) or "
                          "delta_amd/sharded.py over torch.distributed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel table, roofline, pipelines, record "
+                         "checksums, CPU baseline with parity, end-to-end / export legs, config 4's K5 and "
+                         "checkpoint write")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-timing", action="store_true", help="time the steps without the roofline kernel's events")
     ap.add_argument("--profile-steps", type=int, default=3, help="untimed steps with an event pair on every launch")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
@@ -549,11 +624,9 @@ def main():
         staged = eng.stage_log(log_path)
         stage_s = time.perf_counter() - t_stage
 
-        def step():
+        def replay_once():
             st = staged.replay(cutoff)
-            c = st.counts
-            st.release()
-            return c, c
+            return st, st.counts, st.counts
     elif args.driver == "lib":
         from delta_amd.sharded import stage_shard
         box = [Engine.comm_unique_id() if rank == 0 else None]
@@ -562,58 +635,68 @@ def main():
         staged = stage_shard(eng, log_path, world, rank)
         stage_s = time.perf_counter() - t_stage
 
-        def step():
+        def replay_once():
             st = comm.replay_sharded(staged, cutoff)
             c = st.counts  # table-wide counters (all-reduced inside the library)
             lc = st.local_counts()  # this rank's own (K3/K4 pricing)
-            st.release()
-            return c, lc
+            return st, c, lc
     else:
         from delta_amd.sharded import Exchange, replay_sharded, stage_shard
         staged = stage_shard(eng, log_path, world, rank)
         stage_s = time.perf_counter() - t_stage
         ex = Exchange()
 
-        def step():
+        def replay_once():
             st = replay_sharded(staged, cutoff, ex)
-            c, lc = st.counts, st.local.counts
-            st.release()
-            return c, lc
+            return st, st.counts, st.local.counts
+
+    def step(hold=False):
+        """One replay; its state is released at once, or handed back with `hold` (--dump-outputs)."""
+        st, c, lc = replay_once()
+        if hold:
+            return c, lc, st
+        st.release()
+        return c, lc, None
     counts = local_counts = None
-    eng.set_timing(True)  # the first warm-up counts the SNAPPY elements for the roofline accounting
+    eng.set_timing(args.full)  # the first warm-up counts the SNAPPY elements for the roofline accounting
     for i in range(max(args.warmup, 1)):
-        counts, local_counts = step()
+        counts, local_counts, _ = step()
         if i == 0:
             eng.set_timing(False)
     for k in ("num_files", "num_removes", "size_in_bytes", "num_actions", "num_file_actions"):
         assert counts[k] == exp[k], (k, counts[k], exp[k])
     plan = staged.plan()  # this rank's slice (roofline accounting is per rank 0's kernels)
-    # per-kernel table: an untimed pass with an event pair around every launch (one stream, so the
-    # kernels add up to the step); the timed steps then carry events around the longest kernel only
+    # --full, per-kernel table: an untimed pass with an event pair around every launch (one stream, so
+    # the kernels add up to the step); the timed steps then carry events around the longest kernel only
     kern_ms, kern_n, stats = {}, {}, {}
     prof_steps = max(1, args.profile_steps)
-    eng.set_timing(True)
-    for _ in range(prof_steps):
-        step()
-        for k, v in eng.last_timings().items():
-            if k.startswith("stat."):  # counters of the timed replay (k_bucket_verify's pairs, path bytes)
-                stats[k[5:]] = v
-                continue
-            base = k.split("#")[0]
-            kern_ms[base] = kern_ms.get(base, 0.0) + v
-            kern_n[base] = kern_n.get(base, 0) + 1
-    eng.set_timing(False)
-    kern_ms.pop("start", None)
-    kern_ms.pop("end", None)
-    dom = max(kern_ms, key=kern_ms.get) if kern_ms else None
-    eng.set_timing(not args.no_timing and dom is not None, only=dom)
+    dom = None
+    if args.full:
+        eng.set_timing(True)
+        for _ in range(prof_steps):
+            step()
+            for k, v in eng.last_timings().items():
+                if k.startswith("stat."):  # counters of the timed replay (k_bucket_verify's pairs, path bytes)
+                    stats[k[5:]] = v
+                    continue
+                base = k.split("#")[0]
+                kern_ms[base] = kern_ms.get(base, 0.0) + v
+                kern_n[base] = kern_n.get(base, 0) + 1
+        eng.set_timing(False)
+        kern_ms.pop("start", None)
+        kern_ms.pop("end", None)
+        dom = max(kern_ms, key=kern_ms.get) if kern_ms else None
+        eng.set_timing(not args.no_timing and dom is not None, only=dom)
     dom_ms, dom_n = 0.0, 0
+    last = None
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        _, _, last = step(hold=bool(args.dump_outputs) and i == args.steps - 1)
+        if dom is None:
+            continue
         for k, v in eng.last_timings().items():
             if k.split("#")[0] == dom:
                 dom_ms += v
@@ -628,9 +711,37 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     eng.set_timing(False)
+    if last is not None:
+        # what the last timed step returned: its state, read back after the clock has stopped
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last, rows=world == 1)
+        last.release()
     total_actions = counts["num_actions"] * args.steps  # table-wide actions per step
     value = total_actions / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+    out = {
+        "metric": "log actions replayed/sec + achieved HBM GB/s, 1/2/4/8 GPU, 10M-file table",
+        "value": round(value, 1), "unit": "actions/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "u8/int64", "data": "synthetic",
+        "config": {"workload": WORKLOAD.get(args.config, "config %d") % (counts["num_actions"], counts["num_files"]),
+                   "scale": args.scale, "actions": counts["num_actions"],
+                   "json_bytes": exp["json_bytes"], "checkpoint_bytes": exp["checkpoint_bytes"],
+                   "parallelism": ("path-hash shards over %d GPUs (%s all-to-all, %s driver)"
+                                   % (world, "RCCL" if backend == "nccl" else "gloo rehearsal",
+                                      "dr_replay_sharded" if args.driver == "lib" else "torch.distributed"))
+                   if world > 1 else "single GPU"},
+        # the whole step against the HBM roofline: the staged input (JSON + checkpoint bytes, each read
+        # once at least) over the step time
+        "step_frac": round((exp["json_bytes"] + exp["checkpoint_bytes"]) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure and the counters of the replay it timed
+        if rank == 0:
+            out["result"] = {k: counts[k] for k in ("num_files", "num_removes", "size_in_bytes", "live_key_sum",
+                                                    "tomb_key_sum")}
+            print(json.dumps(out), flush=True)
+        return
     kernels = {}
     for k, ms in kern_ms.items():
         per_step = ms / prof_steps
@@ -796,22 +907,8 @@ def main():
     if world == 1 and args.config == 4:
         k5 = measure_filter(eng, staged, cutoff, exp, args.steps)
         ckpt = measure_checkpoint_write(eng, staged, cutoff, parts=100)
-    out = {
-        "metric": "log actions replayed/sec + achieved HBM GB/s, 1/2/4/8 GPU, 10M-file table",
-        "value": round(value, 1), "unit": "actions/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "u8/int64", "data": "synthetic",
-        "config": {"workload": WORKLOAD.get(args.config, "config %d") % (counts["num_actions"], counts["num_files"]),
-                   "scale": args.scale, "actions": counts["num_actions"],
-                   "json_bytes": exp["json_bytes"], "checkpoint_bytes": exp["checkpoint_bytes"],
-                   "parallelism": ("path-hash shards over %d GPUs (%s all-to-all, %s driver)"
-                                   % (world, "RCCL" if backend == "nccl" else "gloo rehearsal",
-                                      "dr_replay_sharded" if args.driver == "lib" else "torch.distributed"))
-                   if world > 1 else "single GPU"},
+    out.update({
         "roofline": roofline,
-        # the whole step against the HBM roofline: the staged input (JSON + checkpoint bytes, each read
-        # once at least) over the step time
-        "step_frac": round((exp["json_bytes"] + exp["checkpoint_bytes"]) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
         "pipelines": pipelines,
         "cpu_baseline": cpu,
         "end_to_end": e2e,
@@ -821,7 +918,7 @@ def main():
         "result": dict({k: counts[k] for k in ("num_files", "num_removes", "size_in_bytes", "live_key_sum",
                                                "tomb_key_sum", "live_record_sum", "tomb_record_sum") if k in counts},
                        record_sums_s=round(record_s, 3) if world == 1 else None),
-    }
+    })
     print(json.dumps(out), flush=True)
 
 

@@ -11,5 +11,5 @@ timeout -k 10 400 python $R/bench.py --config $C --no-cpu-baseline > $O/warm.jso
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python $R/bench.py --config $C --no-cpu-baseline > $O/stats.log 2>&1
 timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$KRE" -d $O/pmc/fetch -o pmc --output-format csv -- python $R/bench.py --config $C --no-cpu-baseline > $O/fetch.log 2>&1
 timeout -s KILL 400 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$KRE" -d $O/pmc/write -o pmc --output-format csv -- python $R/bench.py --config $C --no-cpu-baseline > $O/write.log 2>&1
-timeout -k 10 600 python $R/bench.py --config $C --pmc-dir $O/pmc > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python $R/bench.py --config $C --full --pmc-dir $O/pmc > $O/bench.json 2> $O/bench.err
 cat $O/bench.json

@@ -40,6 +40,59 @@ def test_merge_rank_reports_keeps_missing_pipelines_null():
     assert pipes["sort_reduce"] is None
 
 
+def test_halves_are_exact_for_64_bit_sums():
+    import numpy as np
+    from bench import _halves
+    vals = [0, 1, (1 << 53) + 1, (1 << 64) - 1, 8504151649907663444]
+    h = _halves(vals)
+    assert h.dtype == np.float64 and h.shape == (5, 2)
+    assert [(int(a) << 32) | int(b) for a, b in h] == vals
+
+
+@pytest.mark.gpu
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run: the headline keys without the --full legs, --steps timed steps,
+    and --dump-outputs holding the last step's state as float64 arrays that agree with the line."""
+    import numpy as np
+    import bench
+    out = tmp_path / "dump"
+    env = dict(os.environ, DR_BENCH_DIR=str(tmp_path))
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--scale", "0.03", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "actions/s" and line["higher_is_better"] is True and line["dtype"] == "u8/int64"
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - line["config"]["actions"] / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+    for k in ("roofline", "pipelines", "cpu_baseline", "end_to_end", "kernels"):
+        assert k not in line, k
+    arrays = {f[:-4]: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    counts = dict(zip(bench.DUMP_COUNTS, arrays["counts"]))
+    res = line["result"]
+    assert counts["num_files"] == res["num_files"] and counts["num_removes"] == res["num_removes"]
+    assert counts["size_in_bytes"] == res["size_in_bytes"] and counts["num_actions"] == line["config"]["actions"]
+    ks = [(int(a) << 32) | int(b) for a, b in arrays["key_sums"]]
+    assert ks == [res["live_key_sum"], res["tomb_key_sum"]]
+    # config 3 at this scale: the live side is sampled, the tombstones are dumped whole
+    assert res["num_files"] > bench.DUMP_ROWS > res["num_removes"] > 0
+    live = arrays["live_rows"]
+    assert 0 < len(live) <= bench.DUMP_ROWS and np.all(np.diff(live) > 0) and live[-1] < res["num_files"]
+    assert len(arrays["tombstones_rows"]) == res["num_removes"]
+    for side in ("live", "tombstones"):
+        n = len(arrays[side + "_rows"])
+        assert arrays[side + "_size"].shape == arrays[side + "_path_len"].shape == (n,)
+        assert arrays[side + "_record_hash"].shape == (n, 2)
+    assert arrays["live_modification_time"].shape == live.shape
+    th = arrays["tombstones_record_hash"]
+    tomb_sum = sum((int(a) << 32) | int(b) for a, b in th) % (1 << 64)
+    assert tomb_sum == (int(arrays["record_sums"][1][0]) << 32) | int(arrays["record_sums"][1][1])
+    assert np.all(arrays["tombstones_deletion_timestamp"] > 0)  # the kept removes carry their timestamp
+
+
 @pytest.mark.gpu
 def test_two_rank_gloo_rehearsal_line(tmp_path):
     """`bench.py --gpus 2` with DR_BENCH_BACKEND=gloo on one GPU (torch driver, host-staged exchange):
@@ -47,7 +100,7 @@ def test_two_rank_gloo_rehearsal_line(tmp_path):
     env = dict(os.environ, DR_BENCH_BACKEND="gloo", DR_BENCH_DIR=str(tmp_path))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.02", "--profile-steps", "1"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.02", "--profile-steps", "1", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
