@@ -2860,22 +2860,18 @@ struct DevExport {
   DBuf<int64_t> pv_key_off, pv_val_off, tags_key_off, tags_val_off;  // per entry (entries + 1)
 };
 
-// Records [lo, hi) of the side (export order); the whole side by default. `at` (may be null) is
-// called with 0 once the paths, flags and deletion timestamps are enqueued, 1 once pass 1's scalars
-// and offsets are (before the host waits for their totals), 2 once every column is: a streamed
-// export queues each group's copy to the host there.
-static void export_device(dr_state& st, int which, DevExport& X, uint64_t lo = 0, uint64_t hi = UINT64_MAX,
+// The records of the side whose action indices are didx[0 .. n) (device; any order, repeats allowed:
+// every output is placed by its position in didx). `at` (may be null) is called with 0 once the
+// paths, flags and deletion timestamps are enqueued, 1 once pass 1's scalars and offsets are (before
+// the host waits for their totals), 2 once every column is: a streamed export queues each group's
+// copy to the host there.
+static void export_device_idx(dr_state& st, int which, DevExport& X, const uint32_t* didx, uint64_t n,
                           const std::function<void(int)>* at = nullptr) {
   DR_STAGE("export", st.ctx->stream);
   ensure_ready(st);
   dr_ctx* ctx = st.ctx;
   hipStream_t stream = ctx->stream;
   StagedData& s = *st.sources[0];
-  const uint64_t total = which == DR_LIVE ? st.n_live : st.n_tomb;
-  hi = std::min(hi, total);
-  lo = std::min(lo, hi);
-  const uint64_t n = hi - lo;
-  const uint32_t* didx = (which == DR_LIVE ? st.live.p : st.tomb.p) + lo;
   X.n = n;
   // canonical paths, deletionTimestamp and flags from the action arrays
   X.path_ptr = DBuf<uint64_t>(ctx, n);
@@ -3031,6 +3027,16 @@ static void export_device(dr_state& st, int which, DevExport& X, uint64_t lo = 0
   // a checkpoint record's stats are one contiguous decoded string: copied whole, several lanes each
   launch_gather_bytes(stats_src.p, stats_srclen.p, X.off[EXC_STATS].p, n, X.stats_bytes.p, stream);
   if (at) (*at)(2);
+}
+
+// Records [lo, hi) of the side (export order); the whole side by default.
+static void export_device(dr_state& st, int which, DevExport& X, uint64_t lo = 0, uint64_t hi = UINT64_MAX,
+                          const std::function<void(int)>* at = nullptr) {
+  ensure_ready(st);  // the survivor lists in their final order
+  const uint64_t total = which == DR_LIVE ? st.n_live : st.n_tomb;
+  hi = std::min(hi, total);
+  lo = std::min(lo, hi);
+  export_device_idx(st, which, X, (which == DR_LIVE ? st.live.p : st.tomb.p) + lo, hi - lo, at);
 }
 
 // Both sides' device export columns, built once per state and kept until its release.
@@ -5901,25 +5907,29 @@ int dr_state_nonfile_json(dr_state* state, const char** json, uint64_t* len) {
   return DR_OK;
 }
 
+static void fill_export(dr_export* out, const ExportCols& e, int64_t n) {
+  *out = dr_export{};
+  out->n = n;
+  out->path_off = e.path_off; out->path_bytes = e.path_bytes;
+  out->size = e.size; out->modification_time = e.mtime;
+  out->deletion_timestamp = e.delts; out->deletion_timestamp_valid = e.delts_valid;
+  out->extended_file_metadata = e.efm;
+  out->stats_off = e.stats_off; out->stats_bytes = e.stats_bytes; out->stats_null = e.stats_null;
+  out->pv_entry_off = e.pv_entry_off; out->pv_null = e.pv_null;
+  out->pv_key_off = e.pv_key_off; out->pv_key_bytes = e.pv_key_bytes;
+  out->pv_val_off = e.pv_val_off; out->pv_val_bytes = e.pv_val_bytes; out->pv_val_null = e.pv_val_null;
+  out->tags_entry_off = e.tags_entry_off; out->tags_null = e.tags_null;
+  out->tags_key_off = e.tags_key_off; out->tags_key_bytes = e.tags_key_bytes;
+  out->tags_val_off = e.tags_val_off; out->tags_val_bytes = e.tags_val_bytes;
+  out->tags_val_null = e.tags_val_null;
+}
+
 int dr_state_export(dr_state* state, int32_t which, dr_export* out) {
   if (!state || !out || (which != DR_LIVE && which != DR_TOMBSTONES)) return DR_E_INVALID_ARG;
   return guard(state->ctx, [&] {
     build_export(*state, which);
     ExportCols& e = state->exp[which];
-    *out = dr_export{};
-    out->n = e.n;
-    out->path_off = e.path_off; out->path_bytes = e.path_bytes;
-    out->size = e.size; out->modification_time = e.mtime;
-    out->deletion_timestamp = e.delts; out->deletion_timestamp_valid = e.delts_valid;
-    out->extended_file_metadata = e.efm;
-    out->stats_off = e.stats_off; out->stats_bytes = e.stats_bytes; out->stats_null = e.stats_null;
-    out->pv_entry_off = e.pv_entry_off; out->pv_null = e.pv_null;
-    out->pv_key_off = e.pv_key_off; out->pv_key_bytes = e.pv_key_bytes;
-    out->pv_val_off = e.pv_val_off; out->pv_val_bytes = e.pv_val_bytes; out->pv_val_null = e.pv_val_null;
-    out->tags_entry_off = e.tags_entry_off; out->tags_null = e.tags_null;
-    out->tags_key_off = e.tags_key_off; out->tags_key_bytes = e.tags_key_bytes;
-    out->tags_val_off = e.tags_val_off; out->tags_val_bytes = e.tags_val_bytes;
-    out->tags_val_null = e.tags_val_null;
+    fill_export(out, e, e.n);
   });
 }
 
@@ -6011,20 +6021,155 @@ static void export_range(dr_state& st, int which, uint64_t lo, uint64_t hi, dr_r
   R.block = ctx->host_alloc(group_bytes(cols));
   queue_group(cols, R.block, stream);
   HIP_OK(hipStreamSynchronize(stream));
-  *out = dr_export{};
-  out->n = int64_t(n);
-  out->path_off = ex.path_off; out->path_bytes = ex.path_bytes;
-  out->size = ex.size; out->modification_time = ex.mtime;
-  out->deletion_timestamp = ex.delts; out->deletion_timestamp_valid = ex.delts_valid;
-  out->extended_file_metadata = ex.efm;
-  out->stats_off = ex.stats_off; out->stats_bytes = ex.stats_bytes; out->stats_null = ex.stats_null;
-  out->pv_entry_off = ex.pv_entry_off; out->pv_null = ex.pv_null;
-  out->pv_key_off = ex.pv_key_off; out->pv_key_bytes = ex.pv_key_bytes;
-  out->pv_val_off = ex.pv_val_off; out->pv_val_bytes = ex.pv_val_bytes; out->pv_val_null = ex.pv_val_null;
-  out->tags_entry_off = ex.tags_entry_off; out->tags_null = ex.tags_null;
-  out->tags_key_off = ex.tags_key_off; out->tags_key_bytes = ex.tags_key_bytes;
-  out->tags_val_off = ex.tags_val_off; out->tags_val_bytes = ex.tags_val_bytes;
-  out->tags_val_null = ex.tags_val_null;
+  fill_export(out, ex, int64_t(n));
+}
+
+// ---- selected-rows export (dr_state_export_rows) -------------------------------------------------
+// Rows of one side by position, in the caller's order, as one pinned block owned by a dr_range. A
+// side whose columns are not resident is walked (k_export over the composed action list: only the
+// selected records' lines and checkpoint rows are read, nothing is kept); a resident side is
+// gathered from its columns (k_rows.hip). Both build a DevExport of the selection, whose offsets
+// start at 0 as a range's do, and copy it out the same way.
+
+// Walk path: sel[i] = side list[rows[i]], then the export passes over sel.
+static void rows_walk(dr_state& st, int which, const int64_t* drows, uint64_t n, DevExport& Y) {
+  dr_ctx* ctx = st.ctx;
+  DBuf<uint32_t> sel(ctx, n);
+  launch_rows_compose(which == DR_LIVE ? st.live.p : st.tomb.p, drows, n, sel.p, ctx->stream);
+  export_device_idx(st, which, Y, sel.p, n);
+}
+
+// Gather path: the selection's columns from the side's resident ones.
+static void rows_gather(dr_state& st, const DevExport& X, const int64_t* drows, uint64_t n, DevExport& Y) {
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  Y.n = n;
+  Y.path_off = DBuf<uint64_t>(ctx, n + 1);
+  Y.delts = DBuf<uint64_t>(ctx, n);
+  Y.flags = DBuf<uint8_t>(ctx, n);
+  Y.size = DBuf<int64_t>(ctx, n);
+  Y.mtime = DBuf<int64_t>(ctx, n);
+  Y.efm = DBuf<uint8_t>(ctx, n);
+  Y.stats_null = DBuf<uint8_t>(ctx, n);
+  Y.pv_null = DBuf<uint8_t>(ctx, n);
+  Y.tags_null = DBuf<uint8_t>(ctx, n);
+  for (int k : {EXC_STATS, EXC_PV_N, EXC_TAGS_N}) Y.off[k] = DBuf<uint64_t>(ctx, n + 1);
+  DBuf<uint64_t> path_src(ctx, n), stats_src(ctx, n);
+  DBuf<uint32_t> path_len(ctx, n), stats_len(ctx, n), pv_n(ctx, n), tags_n(ctx, n);
+  RowsArgs a{};
+  a.rows = drows;
+  a.n = n;
+  a.path_off = X.path_off.p; a.path_bytes = X.path_bytes.p;
+  a.size = X.size.p; a.mtime = X.mtime.p; a.delts = X.delts.p; a.flags = X.flags.p; a.efm = X.efm.p;
+  a.stats_null = X.stats_null.p; a.pv_null = X.pv_null.p; a.tags_null = X.tags_null.p;
+  a.stats_off = X.off[EXC_STATS].p; a.stats_bytes = X.stats_bytes.p;
+  a.pv_entry = X.off[EXC_PV_N].p; a.tags_entry = X.off[EXC_TAGS_N].p;
+  a.o_size = Y.size.p; a.o_mtime = Y.mtime.p; a.o_delts = Y.delts.p; a.o_flags = Y.flags.p; a.o_efm = Y.efm.p;
+  a.o_stats_null = Y.stats_null.p; a.o_pv_null = Y.pv_null.p; a.o_tags_null = Y.tags_null.p;
+  a.path_src = path_src.p; a.path_len = path_len.p;
+  a.stats_src = stats_src.p; a.stats_len = stats_len.p;
+  a.pv_n = pv_n.p; a.tags_n = tags_n.p;
+  launch_rows_row(a, stream);
+  DBuf<uint8_t> scratch(ctx, scan_scratch_for(n));
+  uint64_t* const row_off[4] = {Y.path_off.p, Y.off[EXC_STATS].p, Y.off[EXC_PV_N].p, Y.off[EXC_TAGS_N].p};
+  const uint32_t* const row_cnt[4] = {path_len.p, stats_len.p, pv_n.p, tags_n.p};
+  uint64_t row_tot[4] = {};
+  for (int k = 0; k < 4; ++k) {
+    launch_scan_u32(row_cnt[k], row_off[k], n, ss(scratch), stream);
+    if (!n) HIP_OK(hipMemsetAsync(row_off[k], 0, 8, stream));
+  }
+  for (int k = 0; k < 4 && n; ++k) row_tot[k] = d2h_one(row_off[k] + n, stream);
+  Y.path_nb = row_tot[0];
+  Y.tot[EXC_STATS] = row_tot[1];
+  Y.tot[EXC_PV_N] = row_tot[2];
+  Y.tot[EXC_TAGS_N] = row_tot[3];
+  // +16 on every byte buffer: the spare bytes whole-word readers of the columns expect
+  Y.path_bytes = DBuf<uint8_t>(ctx, Y.path_nb + 16);
+  Y.stats_bytes = DBuf<uint8_t>(ctx, Y.tot[EXC_STATS] + 16);
+  launch_gather_bytes(path_src.p, path_len.p, Y.path_off.p, n, Y.path_bytes.p, stream);
+  launch_gather_bytes(stats_src.p, stats_len.p, Y.off[EXC_STATS].p, n, Y.stats_bytes.p, stream);
+  // the two maps: every gathered entry's sources, their lengths scanned into the entry offsets
+  struct MapCols {
+    const DBuf<int64_t>&xk, &xv;
+    const DBuf<uint8_t>&xkb, &xvb, &xvn;
+    DBuf<int64_t>&yk, &yv;
+    DBuf<uint8_t>&ykb, &yvb, &yvn;
+    int cn, ckb, cvb;
+  };
+  const MapCols maps[2] = {
+      {X.pv_key_off, X.pv_val_off, X.pv_key_bytes, X.pv_val_bytes, X.pv_val_null, Y.pv_key_off, Y.pv_val_off,
+       Y.pv_key_bytes, Y.pv_val_bytes, Y.pv_val_null, EXC_PV_N, EXC_PV_KB, EXC_PV_VB},
+      {X.tags_key_off, X.tags_val_off, X.tags_key_bytes, X.tags_val_bytes, X.tags_val_null, Y.tags_key_off,
+       Y.tags_val_off, Y.tags_key_bytes, Y.tags_val_bytes, Y.tags_val_null, EXC_TAGS_N, EXC_TAGS_KB, EXC_TAGS_VB}};
+  for (const MapCols& m : maps) {
+    const uint64_t E = Y.tot[m.cn];
+    m.yk = DBuf<int64_t>(ctx, E + 1);
+    m.yv = DBuf<int64_t>(ctx, E + 1);
+    m.yvn = DBuf<uint8_t>(ctx, E + 1);
+    DBuf<uint64_t> ksrc(ctx, E), vsrc(ctx, E);
+    DBuf<uint32_t> klen(ctx, E), vlen(ctx, E);
+    RowsMapArgs e{};
+    e.rows = drows;
+    e.n = n;
+    e.entry = X.off[m.cn].p;
+    e.key_off = m.xk.p; e.key_bytes = m.xkb.p;
+    e.val_off = m.xv.p; e.val_bytes = m.xvb.p; e.val_null = m.xvn.p;
+    e.out_entry = Y.off[m.cn].p;
+    e.ksrc = ksrc.p; e.klen = klen.p; e.vsrc = vsrc.p; e.vlen = vlen.p; e.o_val_null = m.yvn.p;
+    if (E) launch_rows_entries(e, stream);
+    if (scratch.n < scan_scratch_for(E)) scratch = DBuf<uint8_t>(ctx, scan_scratch_for(E));
+    uint64_t* const ko = reinterpret_cast<uint64_t*>(m.yk.p);
+    uint64_t* const vo = reinterpret_cast<uint64_t*>(m.yv.p);
+    launch_scan_u32(klen.p, ko, E, ss(scratch), stream);
+    launch_scan_u32(vlen.p, vo, E, ss(scratch), stream);
+    if (!E) {
+      HIP_OK(hipMemsetAsync(ko, 0, 8, stream));
+      HIP_OK(hipMemsetAsync(vo, 0, 8, stream));
+    } else {
+      Y.tot[m.ckb] = d2h_one(ko + E, stream);
+      Y.tot[m.cvb] = d2h_one(vo + E, stream);
+    }
+    m.ykb = DBuf<uint8_t>(ctx, Y.tot[m.ckb] + 16);
+    m.yvb = DBuf<uint8_t>(ctx, Y.tot[m.cvb] + 16);
+    launch_gather_bytes(ksrc.p, klen.p, ko, E, m.ykb.p, stream);
+    launch_gather_bytes(vsrc.p, vlen.p, vo, E, m.yvb.p, stream);
+    // (the source and length lists are released after the gathers on the same stream)
+  }
+}
+
+static void export_rows(dr_state& st, int which, const int64_t* rows, uint64_t n, dr_range& R, dr_export* out) {
+  DR_STAGE("export.rows", st.ctx->stream);
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  ensure_ready(st);
+  const uint64_t total = which == DR_LIVE ? st.n_live : st.n_tomb;
+  // refused before the device reads through any of them
+  for (uint64_t i = 0; i < n; ++i)
+    if (rows[i] < 0 || uint64_t(rows[i]) >= total)
+      fail(DR_E_INVALID_ARG, fmt("dr_state_export_rows: rows[%llu] = %lld is outside [0, %llu)", (unsigned long long)i,
+                                 (long long)rows[i], (unsigned long long)total));
+  DBuf<int64_t> drows = upload(ctx, rows, n);
+  DevExport Y;
+  if (st.dexp[which]) {
+    if (st.dexp[which]->n != total) fail(DR_E_INTERNAL, "resident export columns do not cover the side");
+    rows_gather(st, *st.dexp[which], drows.p, n, Y);
+  } else {
+    rows_walk(st, which, drows.p, n, Y);
+  }
+  DBuf<uint8_t> dvalid(ctx, n);
+  DBuf<int64_t> ddelts(ctx, n);
+  launch_delts_fix(Y.flags.p, reinterpret_cast<const int64_t*>(Y.delts.p), n, dvalid.p, ddelts.p, stream);
+  ExportCols ex;  // only its pointer fields: the columns are carved from R.block
+  std::vector<ExportCol> cols;
+  for (int g = 0; g < 3; ++g) {
+    std::vector<ExportCol> c = export_group(ex, Y, g, dvalid.p, ddelts.p);
+    cols.insert(cols.end(), c.begin(), c.end());
+  }
+  R.ctx = ctx;
+  R.block = ctx->host_alloc(group_bytes(cols));
+  queue_group(cols, R.block, stream);
+  HIP_OK(hipStreamSynchronize(stream));
+  fill_export(out, ex, int64_t(n));
 }
 
 // The offsets of the row-level columns at sample rows, and of the entry-level columns at the
@@ -6126,6 +6271,23 @@ int dr_state_export_range(dr_state* state, int32_t which, int64_t row_begin, int
     HIP_OK(hipSetDevice(state->ctx->device));
     auto R = std::make_unique<dr_range>();
     export_range(*state, which, uint64_t(row_begin), uint64_t(row_end), *R, out);
+    std::lock_guard<std::mutex> g(g_ranges_mu);
+    g_ranges.insert(R.get());
+    *range = R.release();
+  });
+}
+
+int dr_state_export_rows(dr_state* state, int32_t which, const int64_t* rows, int64_t nrows, dr_range** range,
+                         dr_export* out) {
+  if (!state || !range || !out) return DR_E_INVALID_ARG;
+  *range = nullptr;
+  return guard(state->ctx, [&] {
+    if (which != DR_LIVE && which != DR_TOMBSTONES) fail(DR_E_INVALID_ARG, fmt("dr_state_export_rows: which = %d is no side", int(which)));
+    if (nrows < 0) fail(DR_E_INVALID_ARG, fmt("dr_state_export_rows: nrows = %lld is negative", (long long)nrows));
+    if (nrows > 0 && !rows) fail(DR_E_INVALID_ARG, "dr_state_export_rows: rows is NULL at position 0");
+    HIP_OK(hipSetDevice(state->ctx->device));
+    auto R = std::make_unique<dr_range>();
+    export_rows(*state, which, rows, uint64_t(nrows), *R, out);
     std::lock_guard<std::mutex> g(g_ranges_mu);
     g_ranges.insert(R.get());
     *range = R.release();

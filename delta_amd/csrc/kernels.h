@@ -806,6 +806,42 @@ struct RecordHashArgs {
 void launch_record_hash(const RecordHashArgs& a, hipStream_t st);
 }  // namespace dr
 
+// ---- selected-rows export (k_rows.hip) -----------------------------------------------------------
+namespace dr {
+// sel[i] = side[rows[i]] (rows: positions in the side's survivor list, every one below its length)
+void launch_rows_compose(const uint32_t* side, const int64_t* rows, uint64_t n, uint32_t* sel, hipStream_t st);
+// Row pass over a side's resident export columns: output row i is side row rows[i].
+struct RowsArgs {
+  const int64_t* rows;  // every one in [0, side rows)
+  uint64_t n;
+  // the side's resident columns (DevExport)
+  const uint64_t* path_off; const uint8_t* path_bytes;
+  const int64_t* size; const int64_t* mtime; const uint64_t* delts; const uint8_t* flags; const uint8_t* efm;
+  const uint8_t* stats_null; const uint8_t* pv_null; const uint8_t* tags_null;
+  const uint64_t* stats_off; const uint8_t* stats_bytes;
+  const uint64_t* pv_entry; const uint64_t* tags_entry;
+  // per selected row
+  int64_t* o_size; int64_t* o_mtime; uint64_t* o_delts; uint8_t* o_flags; uint8_t* o_efm;
+  uint8_t* o_stats_null; uint8_t* o_pv_null; uint8_t* o_tags_null;
+  uint64_t* path_src; uint32_t* path_len;    // the row's path bytes and their length
+  uint64_t* stats_src; uint32_t* stats_len;
+  uint32_t* pv_n; uint32_t* tags_n;          // entry counts
+};
+void launch_rows_row(const RowsArgs& a, hipStream_t st);
+// Entry pass over one map (partitionValues or tags) of the selected rows.
+struct RowsMapArgs {
+  const int64_t* rows;
+  uint64_t n;
+  const uint64_t* entry;      // resident: [side rows + 1] first entry per row
+  const int64_t* key_off; const uint8_t* key_bytes;  // resident: per entry (+ 1)
+  const int64_t* val_off; const uint8_t* val_bytes; const uint8_t* val_null;
+  const uint64_t* out_entry;  // [n + 1] exclusive scan of the selected rows' entry counts
+  // per gathered entry
+  uint64_t* ksrc; uint32_t* klen; uint64_t* vsrc; uint32_t* vlen; uint8_t* o_val_null;
+};
+void launch_rows_entries(const RowsMapArgs& a, hipStream_t st);
+}  // namespace dr
+
 // ---- checkpoint page encoding (k_encode.hip) -----------------------------------------------------
 namespace dr {
 enum EncKind : int32_t { ENC_STR_PTR = 0, ENC_STR_OFF = 1, ENC_I64 = 2, ENC_I32 = 3, ENC_BOOL = 4, ENC_MAP_KEY = 5,

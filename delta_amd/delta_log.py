@@ -410,6 +410,11 @@ class State:
     def _export(self, which: int) -> List[dict]:
         e = N.dr_export()
         self.eng.check(self.eng.lib.dr_state_export(self.h, which, C.byref(e)))
+        return self._records(e, which)
+
+    @staticmethod
+    def _records(e, which: int) -> List[dict]:
+        """The action records of a dr_export's columns (read while their owner lives)."""
         n = e.n
         out = []
         if n == 0:
@@ -533,6 +538,29 @@ class State:
             return {k: v.copy() for k, v in self._columns(e).items()}
         finally:
             self.eng.lib.dr_range_release(h)
+
+    def _export_rows(self, which: int, rows: Sequence[int], read):
+        """dr_state_export_rows: `read(dr_export)` over the selection's columns; the library's range
+        is released before returning."""
+        rows = [int(r) for r in rows]
+        arr = (C.c_int64 * max(len(rows), 1))(*rows)
+        e = N.dr_export()
+        h = C.c_void_p()
+        with self.eng.lock:
+            self.eng.check(self.eng.lib.dr_state_export_rows(self.h, which, arr, len(rows), C.byref(h), C.byref(e)))
+        try:
+            return read(e)
+        finally:
+            self.eng.lib.dr_range_release(h)
+
+    def export_rows(self, which: int, rows: Sequence[int]) -> Dict[str, "object"]:
+        """dr_state_export_rows: rows `rows` of the side (positions in export order; any order,
+        repeats allowed) as columns whose offsets start at 0, copied into numpy arrays."""
+        return self._export_rows(which, rows, lambda e: {k: v.copy() for k, v in self._columns(e).items()})
+
+    def export_rows_records(self, which: int, rows: Sequence[int]) -> List[dict]:
+        """The same rows as action records (`export(which)[r] for r in rows`) without fetching the side."""
+        return self._export_rows(which, rows, lambda e: self._records(e, which))
 
     def filter(self, program) -> List[int]:
         from .predicates import lower_program
@@ -755,6 +783,8 @@ class Snapshot:
     def files_for_scan(self, filters: Sequence) -> List[dict]:
         """PartitionFiltering.filesForScan: metadata-only conjuncts, evaluated on the GPU."""
         sel = self._scan_rows(filters)
+        if sel is not None and self._all is None:
+            return self.state.export_rows_records(N.DR_LIVE, sel)  # the pruned rows alone
         files = self.all_files
         return list(files) if sel is None else [files[i] for i in sel]
 
@@ -799,9 +829,14 @@ class Snapshot:
         from .predicates import cast_partition_value
         schema = self.partition_schema()
         rows = self._scan_rows(partition_filters)
-        files = self.all_files
+        groups = self.state.partition_groups(rows)  # grouped on the GPU
+        if rows is not None and self._all is None:  # the pruned rows alone, fetched in group order
+            order = [i for grp in groups for i in grp]
+            files = dict(zip(order, self.state.export_rows_records(N.DR_LIVE, order)))
+        else:
+            files = self.all_files
         out = []
-        for grp in self.state.partition_groups(rows):  # grouped on the GPU
+        for grp in groups:
             pv = files[grp[0]].get("partitionValues") or {}
             row = tuple(cast_partition_value(pv[c], t) for c, t in schema.items())
             stats = []
@@ -818,18 +853,23 @@ class Snapshot:
         allFiles sorted by (modificationTime, path) -- Spark's string order is the UTF-8 byte
         order -- indexed by that order, then the partition-only filters applied (on the GPU, as
         filterFileList with the "add" prefix). Returns IndexedFile records."""
-        files = self.all_files
         order = self.state.scan_order()  # sorted on the GPU
         rank = {i: r for r, i in enumerate(order)}
         parts = (self.metadata or {}).get("partitionColumns") or []
         from .predicates import is_partition_only, build_program
         # whole filters, not conjuncts (DeltaTableUtils.isPredicatePartitionColumnsOnly, :46-51)
         preds = [f for f in filters if is_partition_only(f, parts)]
-        keep = set(range(len(files)))
         if preds:
             keep = set(self.state.filter(build_program(self.partition_schema(), preds)))
+            kept = [i for i in order if i in keep]
+        else:
+            kept = order
+        if preds and self._all is None:  # the kept rows alone, fetched in scan order
+            files = dict(zip(kept, self.state.export_rows_records(N.DR_LIVE, kept)))
+        else:
+            files = self.all_files
         return [{"version": self.version, "index": rank[i], "add": files[i], "remove": None, "cdc": None,
-                 "isLast": False} for i in order if i in keep]
+                 "isLast": False} for i in kept]
 
     def release(self) -> None:
         """Frees the resident state now (Snapshot.uncache). Snapshots replaced by `update` are not

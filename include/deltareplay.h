@@ -34,7 +34,9 @@ extern "C" {
  *      each fit a bound, e.g. a JVM direct buffer's 2^31 - 1 bytes)
  *   4  dr_ctx_set_option / dr_ctx_get_option (every path-changing choice is a context option; the
  *      library reads no environment variable that changes a result or a code path); a context may be
- *      shared by threads; a range outlives its context */
+ *      shared by threads; a range outlives its context
+ *      added within ABI 4 (no existing entry point changed; a host that wants it looks the symbol up
+ *      and does without when it is absent): dr_state_export_rows */
 #define DR_ABI_VERSION 4
 
 /* Status codes. The JNI shim rethrows the reference's exception class with dr_last_error():
@@ -272,6 +274,33 @@ int dr_state_export_plan(dr_state* state, int32_t which, int64_t max_rows, uint6
 int dr_state_export_range(dr_state* state, int32_t which, int64_t row_begin, int64_t row_end, dr_range** range,
                           dr_export* out);
 int dr_range_release(dr_range* range);
+
+/* Selected-rows export (an addition within ABI 4): rows `rows[0..nrows)` of side `which`, in the
+ * caller's order, as dr_export columns -- the pruned AddFile rows themselves for
+ * PartitionFiltering.filesForScan (D/PartitionFiltering.scala:27-42), TahoeFileIndex.listFiles
+ * (D/files/TahoeFileIndex.scala:58-81) and DeltaSourceSnapshot.initialFiles
+ * (D/files/DeltaSourceSnapshot.scala:53-95), without materialising the side. `rows` are positions in
+ * dr_state_export's order (a dr_filter selection, a dr_state_scan_order prefix, a
+ * dr_state_partition_groups order, ...): output row i is side row rows[i]; any order and repeats are
+ * allowed. Every offset column starts at 0, as a row range's does (path_off[0] = 0, entry offsets
+ * count from the first gathered entry, byte offsets from the first gathered byte), so the columns
+ * equal dr_state_export's gathered at `rows` and rebased. nrows = 0 (rows NULL or not) is valid: n = 0
+ * and every offset array holds the single entry 0. The columns are host memory in one pinned block
+ * owned by *range until dr_range_release, with a row range's lifetime (it may outlive the state and
+ * the context; a second release returns DR_E_INVALID_ARG). For a sharded state the rows are the
+ * rank's own, as in dr_state_export.
+ * DR_E_INVALID_ARG, with a message that names the first offending position, for rows == NULL with
+ * nrows > 0, nrows < 0, a `which` that is no side, or a rows[i] outside [0, the side's rows); the
+ * positions are checked on the host before any device work reads through them, and the state stays
+ * unchanged and usable.
+ * Two device paths, equal in every byte of every column: a side whose columns are resident (after
+ * dr_state_materialize, dr_state_export, dr_state_record_sums, dr_state_export_plan / _range) is
+ * gathered from them; any other side is walked -- only the selected records' JSON lines and
+ * checkpoint rows are read, and nothing stays resident. The first walk of a side of a state with a
+ * checkpoint still decodes that side's checkpoint export columns whole, once (kept with the state
+ * for later calls). */
+int dr_state_export_rows(dr_state* state, int32_t which, const int64_t* rows, int64_t nrows, dr_range** range,
+                         dr_export* out);
 
 /* The full-record state resident in HBM: every field of allFiles and tombstones (path, size,
  * modificationTime / deletionTimestamp, extendedFileMetadata, stats, partitionValues, tags) extracted

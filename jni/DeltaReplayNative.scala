@@ -56,6 +56,11 @@ object DeltaReplayNative {
   /** Rows [lo, hi) with offsets rebased to the range; handleOut(0) receives the range, freed with
    *  rangeRelease (independent of the state). */
   @native def exportRange(state: Long, which: Int, lo: Long, hi: Long, handleOut: Array[Long]): Array[ByteBuffer]
+  /** Rows `rows` (positions in export order: a filter selection, a scanOrder prefix, a partitionGroups
+   *  order; any order, repeats allowed) with offsets from 0 -- the pruned rows without the side's
+   *  export; handleOut(0) receives the range, freed with rangeRelease. IllegalArgumentException for a
+   *  null `rows` or a position outside the side. */
+  @native def exportRows(state: Long, which: Int, rows: Array[Long], handleOut: Array[Long]): Array[ByteBuffer]
   @native def rangeRelease(range: Long): Unit
   @native def filter(state: Long, program: Array[Byte]): Array[Long]
   @native def scanOrder(state: Long): Array[Long]

@@ -531,6 +531,40 @@ NATIVE(jobjectArray, exportRange)(JNIEnv* env, jobject self, jlong state, jint w
   return out;
 }
 
+/* Rows `rows` of a side (positions in export order: a filter selection, a scanOrder prefix, a
+ * partitionGroups order; any order, repeats allowed) as direct buffers whose offsets start at 0
+ * (dr_state_export_rows) -- the pruned AddFile rows of filesForScan / listFiles / initialFiles without
+ * the side's export. handleOut(0) receives the range, released with rangeRelease as a row range is. */
+NATIVE(jobjectArray, exportRows)(JNIEnv* env, jobject self, jlong state, jint which, jlongArray rows,
+                                 jlongArray handle_out) {
+  (void)self;
+  if (!handle_out || (*env)->GetArrayLength(env, handle_out) < 1) {
+    throw_status(env, DR_E_INVALID_ARG, "exportRows: handleOut must hold one element");
+    return NULL;
+  }
+  if (!rows) {
+    throw_status(env, DR_E_INVALID_ARG, "exportRows: rows is null");
+    return NULL;
+  }
+  const jsize nr = (*env)->GetArrayLength(env, rows);
+  jlong* rv = (*env)->GetLongArrayElements(env, rows, NULL);
+  if (!rv) return NULL; /* OutOfMemoryError pending */
+  dr_range* range = NULL;
+  dr_export e;
+  memset(&e, 0, sizeof e);
+  int rc = dr_state_export_rows((dr_state*)(intptr_t)state, which, (const int64_t*)rv, (int64_t)nr, &range, &e);
+  (*env)->ReleaseLongArrayElements(env, rows, rv, JNI_ABORT);
+  CHECK_STATE(env, rc, (intptr_t)state, NULL);
+  jobjectArray out = columns(env, &e, "exportRows: a column over 2^31 - 1 bytes; fetch the rows in several calls");
+  if (!out) {
+    dr_range_release(range);
+    return NULL;
+  }
+  const jlong h = (jlong)(intptr_t)range;
+  (*env)->SetLongArrayRegion(env, handle_out, 0, 1, &h);
+  return out;
+}
+
 NATIVE(void, rangeRelease)(JNIEnv* env, jobject self, jlong range) {
   (void)env; (void)self;
   dr_range_release((dr_range*)(intptr_t)range);
