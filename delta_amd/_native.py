@@ -32,7 +32,8 @@ DR_FLAG_REDUCE64 = 0x4
 ABI_VERSION = 4  # include/deltareplay.h DR_ABI_VERSION
 # context options (include/deltareplay.h enum dr_option)
 OPTIONS = {"overlap": 1, "split": 2, "bucket_bits": 3, "filter_eval": 4, "apply_full": 5, "canon_hint": 6,
-           "json_staged": 7, "host_cache_bytes": 8}
+           "json_staged": 7, "host_cache_bytes": 8, "lookup_key_bits": 9}
+DR_LOOKUP_ABSENT, DR_LOOKUP_LIVE, DR_LOOKUP_TOMBSTONE = 0, 1, 2  # enum dr_lookup_hit
 
 # Exported symbols (checked by tests/test_native_abi.py against include/deltareplay.h).
 SYMBOLS = [
@@ -43,7 +44,7 @@ SYMBOLS = [
     "dr_replay_sharded", "dr_staged_release", "dr_staged_bytes", "dr_staged_plan",
     "dr_replay_staged",
     "dr_replay", "dr_state_release", "dr_state_apply", "dr_state_counts", "dr_state_local_counts", "dr_state_nonfile_json", "dr_state_check_checksum",
-    "dr_state_export", "dr_state_export_plan", "dr_state_export_range", "dr_state_export_rows", "dr_range_release", "dr_state_materialize", "dr_state_record_sums", "dr_state_record_hashes", "dr_state_write_checkpoint", "dr_state_set_nonfile_json", "dr_filter", "dr_state_scan_order", "dr_state_partition_groups", "dr_free", "dr_last_timings", "dr_set_timing", "dr_set_timing_only",
+    "dr_state_export", "dr_state_export_plan", "dr_state_export_range", "dr_state_export_rows", "dr_state_lookup_paths", "dr_range_release", "dr_state_materialize", "dr_state_record_sums", "dr_state_record_hashes", "dr_state_write_checkpoint", "dr_state_set_nonfile_json", "dr_filter", "dr_state_scan_order", "dr_state_partition_groups", "dr_free", "dr_last_timings", "dr_set_timing", "dr_set_timing_only",
     "dr_shard_plan", "dr_stage_log_shard", "dr_shard_begin", "dr_shard_pack", "dr_shard_reduce",
     "dr_shard_finish", "dr_shard_release", "dr_parse_commits", "dr_parsed_release",
 ]
@@ -166,6 +167,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dr_state_export_plan": ([vp, i32, i64, u64, C.POINTER(_P64), _P64], C.c_int),
         "dr_state_export_range": ([vp, i32, i64, i64, C.POINTER(vp), C.POINTER(dr_export)], C.c_int),
         "dr_state_export_rows": ([vp, i32, _P64, i64, C.POINTER(vp), C.POINTER(dr_export)], C.c_int),
+        "dr_state_lookup_paths": ([vp, vp, vp, i64, C.c_uint32, vp, vp], C.c_int),
         "dr_range_release": ([vp], C.c_int),
         "dr_filter": ([vp, C.POINTER(dr_predicate), C.POINTER(_P64), _P64], C.c_int),
         "dr_state_write_checkpoint": ([vp, i32, i32, C.c_uint32, C.c_uint64, C.POINTER(C.POINTER(C.c_uint8)),

@@ -128,6 +128,7 @@ struct dr_ctx {
     int64_t canon_hint = -1;   // DR_OPT_CANON_HINT: arena bytes standing in for the first replay's sizing
     int64_t json_staged = 0;   // DR_OPT_JSON_STAGED: every segment through the staged K1 kernel
     int64_t host_cache_bytes = int64_t(64) << 30;  // DR_OPT_HOST_CACHE_BYTES: pinned blocks kept for reuse
+    int64_t lookup_key_bits = 64;  // DR_OPT_LOOKUP_KEY_BITS: key bits the path index keeps (test hook)
   } opt;
   // Every entry point that takes this context (or a state, range, shard or communicator of it) holds
   // this lock for the call: a context may be shared by host threads (several Spark tasks of one
@@ -826,6 +827,15 @@ struct dr_state {
   // the materialised state (dr_state_materialize): every field of both sides extracted on the device
   // and kept resident -- the reference's cached SingleAction rows (D/util/StateCache.scala:45-68)
   std::shared_ptr<DevExport> dexp[2];
+  // the path index of dr_state_lookup_paths over this state's own survivor lists (k_lookup.hip), built
+  // on the first lookup and kept until the release; never shared with another state of a chain
+  struct LookupIndex {
+    uint64_t cap = 0;       // slots, a power of two >= 2 * survivors
+    uint64_t key_mask = 0;  // DR_OPT_LOOKUP_KEY_BITS as read at build time
+    DBuf<unsigned long long> keys;
+    DBuf<uint32_t> vals;
+  };
+  std::unique_ptr<LookupIndex> lookup;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -5586,6 +5596,7 @@ static int64_t* option_slot(dr_ctx* ctx, int32_t option) {
     case DR_OPT_CANON_HINT: return &o.canon_hint;
     case DR_OPT_JSON_STAGED: return &o.json_staged;
     case DR_OPT_HOST_CACHE_BYTES: return &o.host_cache_bytes;
+    case DR_OPT_LOOKUP_KEY_BITS: return &o.lookup_key_bits;
     default: return nullptr;
   }
 }
@@ -5603,6 +5614,7 @@ int dr_ctx_set_option(dr_ctx* ctx, int32_t option, int64_t value) {
     case DR_OPT_FILTER_EVAL: ok = value >= 0 && value <= 2; break;
     case DR_OPT_CANON_HINT: ok = value >= -1; break;
     case DR_OPT_HOST_CACHE_BYTES: ok = value >= 0; break;
+    case DR_OPT_LOOKUP_KEY_BITS: ok = value >= 1 && value <= 64; break;
     default: break;
   }
   if (!ok) {
@@ -6172,6 +6184,113 @@ static void export_rows(dr_state& st, int which, const int64_t* rows, uint64_t n
   fill_export(out, ex, int64_t(n));
 }
 
+// ---- path lookup (dr_state_lookup_paths) -----------------------------------------------------------
+// The index: {masked replay key -> (side, export position)} over both ordered survivor lists, 12 B a
+// slot, at most half full. Built on the first lookup of the state.
+constexpr uint64_t kLookupMinSlots = 64;
+// A lookup stages its queries in batches of at most kLookupBatchPaths paths and kLookupBatchBytes path
+// bytes (one path over that bound is a batch of its own): per batch one pinned block (query bytes,
+// offsets, results) and on the device the same plus the canonicalisation arena, 2 * bytes + 32 * paths
+// -- about 3 x 32 MiB + 50 B x 2^18 on the device at the bounds, whatever the number of queries.
+constexpr uint64_t kLookupBatchPaths = uint64_t(1) << 18;
+constexpr uint64_t kLookupBatchBytes = uint64_t(32) << 20;
+
+static LookupIndexArgs lookup_index(dr_state& st) {
+  dr_ctx* ctx = st.ctx;
+  const uint64_t n = st.n_live + st.n_tomb;
+  if (!st.lookup) {
+    // export positions carry the side in their top bit (rows stay below 2^30)
+    if (st.n_live >= LOOKUP_TOMB || st.n_tomb >= LOOKUP_TOMB) fail(DR_E_UNSUPPORTED, "dr_state_lookup_paths: a side of 2^31 rows or more");
+    auto ix = std::make_unique<dr_state::LookupIndex>();
+    ix->cap = kLookupMinSlots;
+    while (ix->cap < 2 * n) ix->cap <<= 1;
+    const int64_t bits = ctx->opt.lookup_key_bits;
+    ix->key_mask = bits >= 64 ? ~uint64_t(0) : (uint64_t(1) << bits) - 1;
+    ix->keys = DBuf<unsigned long long>(ctx, ix->cap);
+    ix->vals = DBuf<uint32_t>(ctx, ix->cap);
+    ix->keys.zero(ctx->stream);
+    LookupIndexArgs a{ix->keys.p, ix->vals.p, ix->cap - 1, ix->key_mask, st.key.p,
+                      st.live.p, st.n_live, st.tomb.p, st.n_tomb};
+    launch_lookup_build(a, ctx->stream);
+    st.lookup = std::move(ix);
+  }
+  dr_state::LookupIndex& ix = *st.lookup;
+  // (the action arrays of a chain state are views that ensure_ready refreshes: taken per call)
+  return LookupIndexArgs{ix.keys.p, ix.vals.p, ix.cap - 1, ix.key_mask, st.key.p,
+                         st.live.p, st.n_live, st.tomb.p, st.n_tomb};
+}
+
+static void lookup_check(const uint8_t* path_bytes, const int64_t* path_off, int64_t npaths, uint32_t flags,
+                         const uint8_t* hit, const int64_t* row) {
+  const char* fn = "dr_state_lookup_paths";
+  if (flags != 0) fail(DR_E_INVALID_ARG, fmt("%s: flags = 0x%x (none is defined)", fn, unsigned(flags)));
+  if (npaths < 0) fail(DR_E_INVALID_ARG, fmt("%s: npaths = %lld is negative", fn, (long long)npaths));
+  if (npaths == 0) return;
+  if (!path_bytes || !path_off || !hit || !row)
+    fail(DR_E_INVALID_ARG, fmt("%s: %s is NULL at index 0", fn, !path_bytes ? "path_bytes" : !path_off ? "path_off" : !hit ? "hit" : "row"));
+  if (path_off[0] < 0) fail(DR_E_INVALID_ARG, fmt("%s: path_off[0] = %lld is negative", fn, (long long)path_off[0]));
+  for (int64_t i = 0; i < npaths; ++i) {
+    if (path_off[i + 1] < path_off[i])
+      fail(DR_E_INVALID_ARG, fmt("%s: path_off[%lld] = %lld is below path_off[%lld] = %lld", fn, (long long)(i + 1),
+                                 (long long)path_off[i + 1], (long long)i, (long long)path_off[i]));
+    if (path_off[i + 1] - path_off[i] > int64_t(INT32_MAX))
+      fail(DR_E_INVALID_ARG, fmt("%s: path %lld holds %lld bytes, over 2^31 - 1", fn, (long long)i,
+                                 (long long)(path_off[i + 1] - path_off[i])));
+  }
+}
+
+static void lookup_paths(dr_state& st, const uint8_t* path_bytes, const int64_t* path_off, uint64_t npaths,
+                         uint8_t* hit, int64_t* row) {
+  DR_STAGE("lookup", st.ctx->stream);
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  ensure_ready(st);
+  LookupProbeArgs a{};
+  a.ix = lookup_index(st);
+  a.path_ptr = st.path_ptr.p;
+  a.path_len = st.path_len.p;
+  // one pinned block and one set of device buffers serve every batch (sized by the largest)
+  struct Batch { uint64_t lo, hi; };
+  std::vector<Batch> batches;
+  uint64_t max_n = 0, max_b = 0;
+  for (uint64_t lo = 0; lo < npaths;) {
+    uint64_t hi = lo + 1;
+    const uint64_t lim = std::min(npaths, lo + kLookupBatchPaths);
+    while (hi < lim && uint64_t(path_off[hi + 1] - path_off[lo]) <= kLookupBatchBytes) ++hi;
+    batches.push_back(Batch{lo, hi});
+    max_n = std::max(max_n, hi - lo);
+    max_b = std::max(max_b, uint64_t(path_off[hi] - path_off[lo]));
+    lo = hi;
+  }
+  const uint64_t off_at = (max_b + 16 + 7) & ~uint64_t(7), row_at = off_at + (max_n + 1) * 8, hit_at = row_at + max_n * 8;
+  struct Pinned {
+    dr_ctx* ctx;
+    uint8_t* p;
+    ~Pinned() { ctx->host_release(p); }
+  } pin{ctx, static_cast<uint8_t*>(ctx->host_alloc(hit_at + max_n))};
+  DBuf<uint8_t> dblob(ctx, max_b + 16), darena(ctx, 2 * max_b + 32 * max_n + 16), dhit(ctx, max_n);
+  DBuf<int64_t> doff(ctx, max_n + 1), drow(ctx, max_n);
+  a.blob = dblob.p;
+  a.off = doff.p;
+  a.arena = darena.p;
+  a.hit = dhit.p;
+  a.row = drow.p;
+  for (const Batch& b : batches) {
+    const uint64_t n = b.hi - b.lo, nb = uint64_t(path_off[b.hi] - path_off[b.lo]);
+    std::memcpy(pin.p, path_bytes + path_off[b.lo], nb);
+    std::memcpy(pin.p + off_at, path_off + b.lo, (n + 1) * 8);
+    if (nb) HIP_OK(hipMemcpyAsync(dblob.p, pin.p, nb, hipMemcpyHostToDevice, stream));
+    HIP_OK(hipMemcpyAsync(doff.p, pin.p + off_at, (n + 1) * 8, hipMemcpyHostToDevice, stream));
+    a.n = n;
+    launch_lookup_probe(a, stream);
+    HIP_OK(hipMemcpyAsync(pin.p + row_at, drow.p, n * 8, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(pin.p + hit_at, dhit.p, n, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));  // the block is reused by the next batch
+    std::memcpy(row + b.lo, pin.p + row_at, n * 8);
+    std::memcpy(hit + b.lo, pin.p + hit_at, n);
+  }
+}
+
 // The offsets of the row-level columns at sample rows, and of the entry-level columns at the
 // samples' entries: the byte size of every column of a range between two samples, without copying
 // the columns (dr_state_export_plan).
@@ -6292,6 +6411,29 @@ int dr_state_export_rows(dr_state* state, int32_t which, const int64_t* rows, in
     g_ranges.insert(R.get());
     *range = R.release();
   });
+}
+
+int dr_state_lookup_paths(dr_state* state, const uint8_t* path_bytes, const int64_t* path_off, int64_t npaths,
+                          uint32_t flags, uint8_t* hit, int64_t* row) {
+  if (!state) return DR_E_INVALID_ARG;
+  dr_ctx* ctx = state->ctx;
+  const int rc = guard(ctx, [&] {
+    // the arguments first: nothing is built, staged or read through them before they hold
+    lookup_check(path_bytes, path_off, npaths, flags, hit, row);
+    if (state->sharded)
+      fail(DR_E_UNSUPPORTED, "dr_state_lookup_paths: a sharded state holds this rank's source-side survivors only; "
+                             "a rank-local answer would mislead");
+    if (npaths == 0) return;
+    HIP_OK(hipSetDevice(ctx->device));
+    ctx->begin_call();
+    lookup_paths(*state, path_bytes, path_off, uint64_t(npaths), hit, row);
+    ctx->collect_timings();
+  });
+  if (rc != DR_OK) {
+    std::lock_guard<std::recursive_mutex> g(ctx->api_mu);
+    ctx->drop_timings();
+  }
+  return rc;
 }
 
 int dr_range_release(dr_range* range) {

@@ -842,6 +842,40 @@ struct RowsMapArgs {
 void launch_rows_entries(const RowsMapArgs& a, hipStream_t st);
 }  // namespace dr
 
+// ---- path lookup (k_lookup.hip; dr_state_lookup_paths) ---------------------------------------------
+namespace dr {
+// The path index of one state: open addressing with linear probing over {key, value} slots (12 B a
+// slot), capacity a power of two >= 2 * survivors. A survivor's value is its export position with the
+// side in the top bit (LOOKUP_TOMB); a slot whose key is 0 is empty. Keys are masked to their low
+// key_bits bits (DR_OPT_LOOKUP_KEY_BITS; a masked 0 reads 1), in the build and the probe alike.
+constexpr uint32_t LOOKUP_TOMB = 0x80000000u;
+struct LookupIndexArgs {
+  unsigned long long* keys;  // [cap]
+  uint32_t* vals;            // [cap]
+  uint64_t cap_mask;         // cap - 1
+  uint64_t key_mask;         // the low key_bits bits
+  const uint64_t* key;       // per action
+  const uint32_t* live; uint64_t n_live;  // ordered survivor lists (action indices)
+  const uint32_t* tomb; uint64_t n_tomb;
+};
+// Inserts every survivor; never deduplicates (two survivors with one key claim a slot each).
+void launch_lookup_build(const LookupIndexArgs& a, hipStream_t st);
+// One batch of queries: query i is blob[off[i] - off[0] .. off[i + 1] - off[0]). `arena` holds
+// 2 * (off[n] - off[0]) + 32 * n + 16 bytes (the canonical forms and key bytes of special queries; query
+// i's share starts at 2 * (off[i] - off[0]) + 32 * i), the blob 16 spare bytes behind its last.
+struct LookupProbeArgs {
+  LookupIndexArgs ix;
+  const uint64_t* path_ptr; const uint32_t* path_len;  // per action: the canonical path
+  const uint8_t* blob;
+  const int64_t* off;   // [n + 1]
+  uint64_t n;
+  uint8_t* arena;
+  uint8_t* hit;         // [n] dr_lookup_hit
+  int64_t* row;         // [n] export position, -1 when absent
+};
+void launch_lookup_probe(const LookupProbeArgs& a, hipStream_t st);
+}  // namespace dr
+
 // ---- checkpoint page encoding (k_encode.hip) -----------------------------------------------------
 namespace dr {
 enum EncKind : int32_t { ENC_STR_PTR = 0, ENC_STR_OFF = 1, ENC_I64 = 2, ENC_I32 = 3, ENC_BOOL = 4, ENC_MAP_KEY = 5,

@@ -562,6 +562,27 @@ class State:
         """The same rows as action records (`export(which)[r] for r in rows`) without fetching the side."""
         return self._export_rows(which, rows, lambda e: self._records(e, which))
 
+    def lookup_paths(self, paths: Sequence) -> Tuple["object", "object"]:
+        """dr_state_lookup_paths: for every path (`str`, encoded as UTF-8, or `bytes`; as a log action's
+        `path` field carries it after JSON decoding) the side whose winner it is at the state's cutoff
+        (`hit`: N.DR_LOOKUP_ABSENT / _LIVE / _TOMBSTONE, np.uint8[n]) and its position in that side's
+        export order (`row`: np.int64[n], -1 when absent) -- the numbering of `filter` and
+        `export_rows`."""
+        import numpy as np
+        raw = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in paths]
+        n = len(raw)
+        off = np.zeros(n + 1, dtype=np.int64)
+        if n:
+            np.cumsum(np.fromiter((len(b) for b in raw), dtype=np.int64, count=n), out=off[1:])
+        blob = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)  # never an empty buffer
+        hit = np.zeros(n, dtype=np.uint8)
+        row = np.full(n, -1, dtype=np.int64)
+        if n:
+            with self.eng.lock:
+                self.eng.check(self.eng.lib.dr_state_lookup_paths(self.h, blob.ctypes.data, off.ctypes.data, n, 0,
+                                                                  hit.ctypes.data, row.ctypes.data))
+        return hit, row
+
     def filter(self, program) -> List[int]:
         from .predicates import lower_program
         pred, keep = lower_program(program)
@@ -787,6 +808,51 @@ class Snapshot:
             return self.state.export_rows_records(N.DR_LIVE, sel)  # the pruned rows alone
         files = self.all_files
         return list(files) if sel is None else [files[i] for i in sel]
+
+    def files_by_path(self, paths: Sequence) -> List[Optional[dict]]:
+        """The AddFile of every path that is a live file of this snapshot, None for every other one --
+        the lookup DeltaCommand.generateCandidateFileMap's host map serves
+        (D/commands/DeltaCommand.scala:96-104), answered by the state's device path index
+        (dr_state_lookup_paths). Paths are canonicalised as the replay does; only the hit rows are
+        fetched (one dr_state_export_rows), or indexed from `all_files` when that is cached."""
+        hit, row = self.state.lookup_paths(paths)
+        at = [i for i in range(len(hit)) if hit[i] == N.DR_LOOKUP_LIVE]
+        rows = [int(row[i]) for i in at]
+        if self._all is not None:
+            recs = [self._all[r] for r in rows]
+        else:
+            recs = self.state.export_rows_records(N.DR_LIVE, rows) if rows else []
+        out: List[Optional[dict]] = [None] * len(hit)
+        for i, rec in zip(at, recs):
+            out[i] = rec
+        return out
+
+    def touched_files(self, paths: Sequence[str]) -> List[dict]:
+        """DeltaCommand.getTouchedFile over `paths` (D/commands/DeltaCommand.scala:159-168): the AddFile
+        of every file a DELETE / UPDATE / MERGE read, from the names input_file_name() gave. A path
+        under the table's data path (that string followed by '/') is relativised by removing the
+        prefix, anything else is looked up as it is. The first path that is no live file raises
+        IllegalStateException (the reference's message without its list of every candidate)."""
+        prefix = self.delta_log.data_path + "/"
+        rel = [p[len(prefix):] if p.startswith(prefix) else p for p in paths]
+        found = self.files_by_path(rel)
+        for p, f in zip(paths, found):
+            if f is None:
+                e = DeltaError(N.DR_OK, "File (%s) to be rewritten not found among candidate files" % p)
+                e.kind = "IllegalStateException"
+                raise e
+        return found
+
+    def unreferenced(self, paths: Sequence) -> List[int]:
+        """The indices of the paths that are neither a live file nor an unexpired tombstone of this
+        snapshot: the left-anti join at the heart of VACUUM (D/commands/VacuumCommand.scala:185-206),
+        where `paths` are the listed files relative to the table (or absolute) and the result is what
+        may be deleted. The state's retention cutoff must be the caller's `deleteBeforeTimestamp - 1`:
+        the reference keeps a tombstone with delTimestamp >= deleteBeforeTimestamp
+        (VacuumCommand.scala:129-161), this state one with delTimestamp > its cutoff. The directories
+        the reference's join also keeps (every parent of a referenced file) are the caller's business."""
+        hit, _ = self.state.lookup_paths(paths)
+        return [i for i in range(len(hit)) if hit[i] == N.DR_LOOKUP_ABSENT]
 
     @property
     def checksum_opt(self) -> Optional[bytes]:

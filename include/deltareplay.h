@@ -36,7 +36,8 @@ extern "C" {
  *      library reads no environment variable that changes a result or a code path); a context may be
  *      shared by threads; a range outlives its context
  *      added within ABI 4 (no existing entry point changed; a host that wants it looks the symbol up
- *      and does without when it is absent): dr_state_export_rows */
+ *      and does without when it is absent): dr_state_export_rows; dr_state_lookup_paths with
+ *      DR_OPT_LOOKUP_KEY_BITS */
 #define DR_ABI_VERSION 4
 
 /* Status codes. The JNI shim rethrows the reference's exception class with dr_last_error():
@@ -160,10 +161,14 @@ enum dr_option {
                                   undersized arena is detected and the parse redone) */
   DR_OPT_JSON_STAGED = 7,      /* 0 (default); 1: every JSON segment through the staged, wave-cooperative
                                   K1 kernel (the streamed-commit walker) instead of the lane-per-line one */
-  DR_OPT_HOST_CACHE_BYTES = 8  /* bytes of released pinned host blocks kept for reuse (default 64 GiB:
+  DR_OPT_HOST_CACHE_BYTES = 8, /* bytes of released pinned host blocks kept for reuse (default 64 GiB:
                                   config 4's 36 GB export stays pinned between snapshots); a released
                                   block evicts the largest cached ones to fit, one over the bound is
                                   unpinned at once */
+  DR_OPT_LOOKUP_KEY_BITS = 9   /* test hook: 64 (default); n in 1..64: the path index of
+                                  dr_state_lookup_paths keeps only the low n bits of every replay key, in
+                                  its build and its probes, so distinct paths share keys and probe runs
+                                  grow long. Read when a state's index is built (its first lookup) */
 };
 int dr_ctx_set_option(dr_ctx* ctx, int32_t option, int64_t value);
 int dr_ctx_get_option(dr_ctx* ctx, int32_t option, int64_t* value);
@@ -301,6 +306,38 @@ int dr_range_release(dr_range* range);
  * for later calls). */
 int dr_state_export_rows(dr_state* state, int32_t which, const int64_t* rows, int64_t nrows, dr_range** range,
                          dr_export* out);
+
+/* Path lookup (an addition within ABI 4): is each of `npaths` paths in the state, on which side, and at
+ * which export position? The state-side question of DeltaCommand.generateCandidateFileMap / getTouchedFile
+ * (D/commands/DeltaCommand.scala:96-104,159-168: DELETE, UPDATE and MERGE turn input_file_name() back
+ * into AddFiles), of VacuumCommand's left-anti join of the directory listing against the live files and
+ * the unexpired tombstones (D/commands/VacuumCommand.scala:129-161,185-206) and of
+ * OptimisticTransaction.checkForConflicts (D/OptimisticTransaction.scala:829-833), answered on the
+ * device instead of from a host map over an exported side.
+ * Query i is the bytes path_bytes[path_off[i] .. path_off[i + 1]) (path_off has npaths + 1 entries): a
+ * path as a log action's `path` field carries it after JSON decoding -- UTF-8, URI-encoded as the log
+ * has it, not JSON-escaped. The library canonicalises and keys each query exactly as the replay does
+ * its actions (D/Snapshot.scala:317-328): a scheme-less absolute path gets '//' collapsed and a trailing
+ * '/' dropped and becomes "file://" + path; "file:/x" and "file:///x" are one key; everything else is
+ * its own canonical form.
+ * hit[i] (dr_lookup_hit) names the side whose winner has that key at the state's own retention cutoff,
+ * row[i] its position in dr_state_export's order of that side -- the numbering of dr_filter and
+ * dr_state_export_rows -- or -1 when absent. A path whose last action is an expired remove, or that was
+ * never seen, is DR_LOOKUP_ABSENT. Duplicate queries are answered independently. hit and row are
+ * caller-owned host arrays of npaths entries. A hit is reported only after the query's canonical bytes
+ * compared equal to the winner's (64-bit key collisions cost a longer probe, never a wrong answer or an
+ * error).
+ * The first call builds the state's path index on the device (12 bytes a slot, two slots or more per
+ * surviving record), kept until dr_state_release; queries are staged in bounded batches, so the
+ * call's own memory does not grow with npaths. npaths = 0 is valid and touches nothing.
+ * DR_E_INVALID_ARG, with a message naming the first offending index, for flags != 0, npaths < 0, a NULL
+ * array with npaths > 0, path_off[0] < 0, a decreasing offset, or a path longer than 2^31 - 1 bytes; the
+ * offsets are checked on the host before the device reads through them, and the state stays unchanged
+ * and usable. DR_E_UNSUPPORTED for a sharded state (dr_replay_sharded / dr_shard_finish): a rank holds
+ * the survivors it parsed, not the ones it owns, so a rank-local answer would mislead. */
+enum dr_lookup_hit { DR_LOOKUP_ABSENT = 0, DR_LOOKUP_LIVE = 1, DR_LOOKUP_TOMBSTONE = 2 };
+int dr_state_lookup_paths(dr_state* state, const uint8_t* path_bytes, const int64_t* path_off, int64_t npaths,
+                          uint32_t flags, uint8_t* hit, int64_t* row);
 
 /* The full-record state resident in HBM: every field of allFiles and tombstones (path, size,
  * modificationTime / deletionTimestamp, extendedFileMetadata, stats, partitionValues, tags) extracted

@@ -61,6 +61,13 @@ object DeltaReplayNative {
    *  export; handleOut(0) receives the range, freed with rangeRelease. IllegalArgumentException for a
    *  null `rows` or a position outside the side. */
   @native def exportRows(state: Long, which: Int, rows: Array[Long], handleOut: Array[Long]): Array[ByteBuffer]
+  /** Path lookup (dr_state_lookup_paths): path i is pathBytes(pathOff(i) until pathOff(i + 1)), UTF-8 as
+   *  an action's `path` carries it; hitOut(i) receives 0 (absent), 1 (a live file) or 2 (an unexpired
+   *  tombstone) and rowOut(i) its position in that side's export order (-1 when absent), the numbering
+   *  of filter and exportRows. What DeltaCommand.getTouchedFile, VacuumCommand's anti-join and
+   *  checkForConflicts ask of allFiles. IllegalArgumentException for a null array, outputs shorter than
+   *  pathOff.length - 1, or offsets outside pathBytes; UnsupportedOperationException for a sharded state. */
+  @native def lookupPaths(state: Long, pathBytes: Array[Byte], pathOff: Array[Long], hitOut: Array[Byte], rowOut: Array[Long]): Unit
   @native def rangeRelease(range: Long): Unit
   @native def filter(state: Long, program: Array[Byte]): Array[Long]
   @native def scanOrder(state: Long): Array[Long]

@@ -565,6 +565,59 @@ NATIVE(jobjectArray, exportRows)(JNIEnv* env, jobject self, jlong state, jint wh
   return out;
 }
 
+/* Path lookup (dr_state_lookup_paths): query i is pathBytes[pathOff(i) .. pathOff(i + 1)) -- a path as an
+ * action's `path` field carries it, UTF-8 -- and hitOut(i) / rowOut(i) receive its side (0 absent, 1 live,
+ * 2 tombstone) and export position (-1 when absent): DeltaCommand.getTouchedFile's, VacuumCommand's and
+ * checkForConflicts' question of the resident state, without a host map over allFiles. The number of
+ * paths is pathOff.length - 1 (a Java array: at most 2^31 - 2). Refused here, before the library is
+ * called: a null array, an empty pathOff, outputs shorter than the paths, a last offset beyond
+ * pathBytes (the library checks that the offsets start at 0 or above and never decrease, so every
+ * one then lies inside the array). The outputs are written back only when the library succeeded;
+ * every pinned or copied array is handed back on every path out. */
+NATIVE(void, lookupPaths)(JNIEnv* env, jobject self, jlong state, jbyteArray path_bytes, jlongArray path_off,
+                          jbyteArray hit_out, jlongArray row_out) {
+  (void)self;
+  if (!path_bytes || !path_off || !hit_out || !row_out) {
+    throw_status(env, DR_E_INVALID_ARG, !path_bytes ? "lookupPaths: pathBytes is null"
+                                        : !path_off ? "lookupPaths: pathOff is null"
+                                        : !hit_out  ? "lookupPaths: hitOut is null"
+                                                    : "lookupPaths: rowOut is null");
+    return;
+  }
+  const jsize noff = (*env)->GetArrayLength(env, path_off);
+  if (noff < 1) {
+    throw_status(env, DR_E_INVALID_ARG, "lookupPaths: pathOff must hold one offset more than there are paths");
+    return;
+  }
+  const jsize n = noff - 1;
+  if ((*env)->GetArrayLength(env, hit_out) < n || (*env)->GetArrayLength(env, row_out) < n) {
+    throw_status(env, DR_E_INVALID_ARG, "lookupPaths: hitOut or rowOut is shorter than the paths");
+    return;
+  }
+  const jsize nbytes = (*env)->GetArrayLength(env, path_bytes);
+  jlong* off = (*env)->GetLongArrayElements(env, path_off, NULL);
+  if (!off) return; /* OutOfMemoryError pending */
+  if (off[n] > (jlong)nbytes) {
+    (*env)->ReleaseLongArrayElements(env, path_off, off, JNI_ABORT);
+    throw_status(env, DR_E_INVALID_ARG, "lookupPaths: the last offset lies beyond pathBytes");
+    return;
+  }
+  jbyte* pb = (*env)->GetByteArrayElements(env, path_bytes, NULL);
+  jbyte* hit = pb ? (*env)->GetByteArrayElements(env, hit_out, NULL) : NULL;
+  jlong* row = hit ? (*env)->GetLongArrayElements(env, row_out, NULL) : NULL;
+  int rc = DR_OK;
+  if (row) /* else OutOfMemoryError pending */
+    rc = dr_state_lookup_paths((dr_state*)(intptr_t)state, (const uint8_t*)pb, (const int64_t*)off, (int64_t)n, 0u,
+                               (uint8_t*)hit, (int64_t*)row);
+  const jint mode = row && rc == DR_OK ? 0 : JNI_ABORT;
+  if (row) (*env)->ReleaseLongArrayElements(env, row_out, row, mode);
+  if (hit) (*env)->ReleaseByteArrayElements(env, hit_out, hit, mode);
+  if (pb) (*env)->ReleaseByteArrayElements(env, path_bytes, pb, JNI_ABORT);
+  (*env)->ReleaseLongArrayElements(env, path_off, off, JNI_ABORT);
+  if (!row) return;
+  CHECK_STATE(env, rc, (intptr_t)state, );
+}
+
 NATIVE(void, rangeRelease)(JNIEnv* env, jobject self, jlong range) {
   (void)env; (void)self;
   dr_range_release((dr_range*)(intptr_t)range);
