@@ -3,10 +3,10 @@
 // backslash, structural, space, control); escapes and string state are resolved on those masks
 // with carries from the previous window (the bit-parallel quote/escape method of simdjson, on
 // 16-bit lanes), which yields the window's token mask. A table-free DFA then consumes only the
-// tokens (brackets, ':', ',', quotes, scalar starts) -- about 45 per add line instead of ~330
-// bytes -- validating JSON grammar and extracting the SingleAction envelope (unwrap priority,
-// D/actions/actions.scala:523-541) and the add/remove path, size and deletionTimestamp
-// (AddFile/RemoveFile field names, D/actions/actions.scala:220-320).
+// tokens (brackets, strings, scalars; a ':' or ',' rides as a flag on the token before it) -- about
+// 20 per add line instead of ~330 bytes -- validating JSON grammar and extracting the SingleAction
+// envelope (unwrap priority, D/actions/actions.scala:523-541) and the add/remove path, size and
+// deletionTimestamp (AddFile/RemoveFile field names, D/actions/actions.scala:220-320).
 //
 // Semantics match Spark's JSON reader over Action.logSchema in PERMISSIVE mode
 // (D/DeltaLogFileIndex.scala:67): a line that is not a valid JSON object is a null row (K_ERROR,
@@ -195,14 +195,27 @@ JL_HD uint8_t file_key(const uint8_t* s, uint32_t n) {
 }
 
 // ---- phase 1: tokenizer ----------------------------------------------------------------------------
-// A token is one u32: line offset << 16 | aux << 4 | class. Scalars are emitted when their run
-// ends, with aux = run length, so phase 2 never scans for a scalar's end.
+// A token is one u32: line offset << 16 | aux << 6 | flags << 4 | class. Scalars are emitted when
+// their run ends, with aux = run length, so phase 2 never scans for a scalar's end.
 // T_STRING / T_STRING_ESC: a whole string (offset of its opening quote, body length in aux) -- one
-// token instead of an open/close pair when the body is shorter than 4096 bytes.
+// token instead of an open/close pair when the body is at most TOK_MAX_AUX bytes.
+// T_SCALAR_LONG: a scalar run longer than TOK_MAX_AUX; its length takes the aux and flag bits.
+//
+// A ':' or ',' is grammatically a property of the token before it (S_COLON -> S_VALUE, S_AFTER ->
+// S_KEY / S_VALUE), so it is not a token of its own: it sets TF_COLON / TF_COMMA on the previous
+// token of the line, which the tokenizer holds back by one (Tokenizer::pend) until the next token or
+// the line end. The DFA applies the flag after the token's own transition with the checks a
+// stand-alone ':' / ',' gets. Punctuation that has no token to ride on (the first token of a line, a
+// second ':' / ',' in a row, after a T_SCALAR_LONG) is still emitted as T_COLON / T_COMMA.
 enum : uint32_t { T_OBJ_OPEN = 0, T_ARR_OPEN, T_OBJ_CLOSE, T_ARR_CLOSE, T_COLON, T_COMMA, T_STR_OPEN,
-                  T_STR_CLOSE, T_STR_CLOSE_ESC, T_SCALAR, T_STRING, T_STRING_ESC };
+                  T_STR_CLOSE, T_STR_CLOSE_ESC, T_SCALAR, T_STRING, T_STRING_ESC, T_SCALAR_LONG = 13 };
+enum : uint32_t { TF_COLON = 0x10u, TF_COMMA = 0x20u, TF_MASK = 0x30u };
 constexpr uint32_t TOK_MAX_LINE = 65535;   // longer lines go to the General walker
 constexpr uint32_t TOK_MAX_SCALAR = 4095;
+constexpr uint32_t TOK_MAX_AUX = 1023;
+constexpr uint32_t TOK_NONE = 0xFFFFFFFFu;  // no token (class 15, both flags: never folded onto)
+// classes that take no flag: stand-alone punctuation, and T_SCALAR_LONG (its length is in those bits)
+constexpr uint32_t TOK_NOFOLD = (1u << T_COLON) | (1u << T_COMMA) | (1u << T_SCALAR_LONG);
 
 // Up to 20 bytes at s as little-endian words (w[0] holds s[0..3]). Bytes at or past n are
 // unspecified: on the device they come from the line buffer (zero-padded past its end), on the
@@ -302,10 +315,17 @@ JL_UNROLL
   return SC_INT;
 }
 
-JL_HD uint32_t tok_make(uint32_t off, uint32_t aux, uint32_t cls) { return (off << 16) | (aux << 4) | cls; }
+JL_HD uint32_t tok_make(uint32_t off, uint32_t aux, uint32_t cls) { return (off << 16) | (aux << 6) | cls; }
 JL_HD uint32_t tok_off(uint32_t t) { return t >> 16; }
-JL_HD uint32_t tok_aux(uint32_t t) { return (t >> 4) & 0xFFFu; }
+JL_HD uint32_t tok_aux(uint32_t t) { return (t >> 6) & 0x3FFu; }
 JL_HD uint32_t tok_cls(uint32_t t) { return t & 0xFu; }
+JL_HD uint32_t tok_long_len(uint32_t t) { return (t >> 4) & 0xFFFu; }  // T_SCALAR_LONG
+// the folded punctuation of a token (none on a T_SCALAR_LONG)
+JL_HD uint32_t tok_flags(uint32_t t) { return tok_cls(t) == T_SCALAR_LONG ? 0u : (t & TF_MASK); }
+// a scalar run of 1..TOK_MAX_SCALAR bytes
+JL_HD uint32_t tok_scalar(uint32_t start, uint32_t len) {
+  return len <= TOK_MAX_AUX ? tok_make(start, len, T_SCALAR) : ((start << 16) | (len << 4) | T_SCALAR_LONG);
+}
 
 enum : uint8_t { ST_OK = 0, ST_BAD = 1, ST_HARD = 2 };
 
@@ -315,8 +335,16 @@ struct Tokenizer {
   uint32_t sc_start = 0;     // line offset where the open scalar run began
   uint32_t sc_bytes = 0;     // scalar bytes seen (each must belong to a validated scalar)
   uint32_t str_open = 0;     // line offset of the open string's quote
+  uint32_t pend = TOK_NONE;  // the line's latest token, held back for a ':' / ',' that may follow
   uint8_t status = ST_OK;
 };
+
+// The next token of the line: the one held back goes out, this one waits for its punctuation.
+template <typename Emit>
+JL_HD void tok_put(Tokenizer& tz, uint32_t t, Emit&& emit) {
+  if (tz.pend != TOK_NONE) emit(tz.pend);
+  tz.pend = t;
+}
 
 // Loads the aligned 16-byte window at a (a is 16-byte aligned; the buffer is readable there).
 JL_HD void load_window(const uint8_t* a, uint32_t w[4]) {
@@ -401,7 +429,7 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
     const uint32_t end = uint32_t(lo);  // one past the run
     const uint32_t len = end - tz.sc_start;
     if (len > TOK_MAX_SCALAR) { tz.status = ST_BAD; return; }
-    emit(tok_make(tz.sc_start, len, T_SCALAR));
+    tok_put(tz, tok_scalar(tz.sc_start, len), emit);
   }
   const uint32_t sc_begin = sc & ~(((sc << 1) | tz.sc_carry) & 0xFFFFu);
   const uint32_t sc_end = sc & ~(sc >> 1) & 0x7FFFu;  // run ends inside this window
@@ -434,17 +462,22 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
         has_bs = tz.pend_bs || (m.bs & below) != 0;
       }
       const uint32_t len = off - open_off - 1u;
-      if (len < 4096u) {
-        emit(tok_make(open_off, len, has_bs ? T_STRING_ESC : T_STRING));
+      if (len <= TOK_MAX_AUX) {
+        tok_put(tz, tok_make(open_off, len, has_bs ? T_STRING_ESC : T_STRING), emit);
       } else {
-        emit(tok_make(open_off, 0, T_STR_OPEN));
-        emit(tok_make(off, 0, has_bs ? T_STR_CLOSE_ESC : T_STR_CLOSE));
+        tok_put(tz, tok_make(open_off, 0, T_STR_OPEN), emit);
+        tok_put(tz, tok_make(off, 0, has_bs ? T_STR_CLOSE_ESC : T_STR_CLOSE), emit);
       }
     } else if (st & bit) {
       const uint32_t c = win_byte(w, k);
-      const uint32_t cls = c == ':' ? T_COLON : c == ',' ? T_COMMA
-                         : ((c & 2u) ? T_OBJ_OPEN : T_OBJ_CLOSE) + ((c & 0x20u) ? 0u : 1u);
-      emit(tok_make(off, 0, cls));
+      if (c == ':' || c == ',') {
+        // folds onto the token held back unless that one has its punctuation already, or takes none
+        const uint32_t pd = tz.pend;
+        if ((pd & TF_MASK) == 0 && !((TOK_NOFOLD >> tok_cls(pd)) & 1u)) tz.pend = pd | (c == ':' ? TF_COLON : TF_COMMA);
+        else tok_put(tz, tok_make(off, 0, c == ':' ? T_COLON : T_COMMA), emit);
+      } else {
+        tok_put(tz, tok_make(off, 0, ((c & 2u) ? T_OBJ_OPEN : T_OBJ_CLOSE) + ((c & 0x20u) ? 0u : 1u)), emit);
+      }
     } else {  // a scalar run ends at k
       // its start is in this window (a begin bit at or below k) or carried from an earlier one
       const uint32_t bb = begins & ((bit << 1) - 1u);
@@ -456,7 +489,7 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
       }
       const uint32_t len = off + 1 - start;
       if (len > TOK_MAX_SCALAR) { tz.status = ST_BAD; return; }
-      emit(tok_make(start, len, T_SCALAR));
+      tok_put(tz, tok_scalar(start, len), emit);
     }
   }
   if (begins) tz.sc_start = uint32_t(lo + int32_t(ctz32(begins)));  // a run that continues
@@ -472,15 +505,19 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
   }
 }
 
-// Line end: a scalar running to the last byte.
+// Line end: a scalar running to the last byte, then the token held back.
 template <typename Emit>
 JL_HD void tokenize_end(uint32_t n, Tokenizer& tz, Emit&& emit) {
-  if (tz.status == ST_OK && tz.in_str) emit(tok_make(tz.str_open, 0, T_STR_OPEN));  // never closed
+  if (tz.status == ST_OK && tz.in_str) tok_put(tz, tok_make(tz.str_open, 0, T_STR_OPEN), emit);  // never closed
   if (tz.status == ST_OK && tz.sc_carry) {
     const uint32_t len = n - tz.sc_start;
     if (len > TOK_MAX_SCALAR) { tz.status = ST_BAD; return; }
-    emit(tok_make(tz.sc_start, len, T_SCALAR));
+    tok_put(tz, tok_scalar(tz.sc_start, len), emit);
     tz.sc_carry = 0;
+  }
+  if (tz.status == ST_OK && tz.pend != TOK_NONE) {
+    emit(tz.pend);
+    tz.pend = TOK_NONE;
   }
 }
 
@@ -648,12 +685,12 @@ JL_HD void dfa_str_close(const uint8_t* p, uint32_t off, bool has_bs, Dfa<Genera
   }
 }
 
-// One token through the JSON grammar and the Action.logSchema extraction.
+// One token's own transition through the JSON grammar and the Action.logSchema extraction.
 template <bool General>
-JL_HD void dfa_token(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
+JL_HD void dfa_token_own(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
   const uint32_t cls = tok_cls(tok), off = tok_off(tok);
   const uint8_t stt = d.state;
-  if (cls >= T_STRING) {
+  if (cls == T_STRING || cls == T_STRING_ESC) {
     if (dfa_str_open(off, d)) dfa_str_close(p, off + 1 + tok_aux(tok), cls == T_STRING_ESC, d);
     return;
   }
@@ -665,9 +702,9 @@ JL_HD void dfa_token(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
     dfa_str_close(p, off, cls == T_STR_CLOSE_ESC, d);
     return;
   }
-  if (cls == T_SCALAR) {
+  if (cls == T_SCALAR || cls == T_SCALAR_LONG) {
     if (!(stt == S_VALUE || stt == S_ARR_FIRST)) { d.status = ST_BAD; return; }
-    const uint32_t L = tok_aux(tok);
+    const uint32_t L = cls == T_SCALAR ? tok_aux(tok) : tok_long_len(tok);
     int64_t v = 0;
     const uint8_t sc = scalar_fast(p + off, L, &v);
     if (sc == SC_BAD) { d.status = ST_BAD; return; }
@@ -756,6 +793,19 @@ JL_HD void dfa_token(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
     --d.depth;
     d.state = d.depth == 0 ? S_DONE : S_AFTER;
   }
+}
+
+// One token: its own transition, then the ':' or ',' folded onto it, checked as the stand-alone
+// T_COLON / T_COMMA is (a ':' needs S_COLON, a ',' needs S_AFTER inside a container).
+template <bool General>
+JL_HD void dfa_token(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
+  dfa_token_own<General>(p, tok, d);
+  const uint32_t fl = tok_flags(tok);
+  if (fl == 0 || d.status != ST_OK) return;
+  const bool colon = (fl & TF_COLON) != 0;
+  const bool ok = fl != TF_MASK && (colon ? d.state == S_COLON : (d.state == S_AFTER && d.depth != 0));
+  if (!ok) { d.status = ST_BAD; return; }
+  d.state = (colon || d.is_arr(d.depth)) ? S_VALUE : S_KEY;
 }
 
 template <bool General>

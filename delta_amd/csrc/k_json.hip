@@ -220,8 +220,12 @@ __device__ __forceinline__ void emit_line(const JsonParseArgs& a, uint64_t line,
 #endif
 constexpr int JL_TOKCAP = DR_JL_TOKCAP;
 #ifndef DR_JL_FLUSH
-#define DR_JL_FLUSH (DR_JL_TOKCAP - 16)  // a window adds at most 16 tokens
+// A window adds at most 17 tokens (a scalar run that ended with the previous window, or a long
+// string's open / close pair, and 15 or 16 more bytes that are tokens), the last one 18: the token the
+// tokenizer held back across the window boundary is not in the count yet.
+#define DR_JL_FLUSH (DR_JL_TOKCAP - 18)
 #endif
+static_assert(DR_JL_FLUSH >= 0 && DR_JL_FLUSH + 18 <= DR_JL_TOKCAP, "a window's tokens must fit behind the flush mark");
 constexpr int JL_FLUSH = DR_JL_FLUSH;
 
 #ifndef DR_JL_BATCH
@@ -259,6 +263,7 @@ __device__ __forceinline__ void walk_line(const JsonParseArgs& a, uint32_t* tokb
   uint4 batch[DR_JL_BATCH];
 #endif
   auto push = [&](uint32_t t) {
+    DR_LDS_CHECK(nt < uint32_t(JL_TOKCAP), "walk_line tokbuf", nt, JL_TOKCAP);
     tokbuf[nt * JL_T + lane] = t;
     ++nt;
   };
@@ -333,6 +338,10 @@ __device__ __forceinline__ void walk_line(const JsonParseArgs& a, uint32_t* tokb
 // outside a string, a newline inside a string, an escape other than \" \\ \/ \b \f \n \r \t, a
 // string of 4096 bytes or more, or more tokens than the tape holds sends the whole wave (a
 // wave-uniform branch) to the per-lane walker, which decides every line exactly as before.
+//
+// The tape has its own token word (offset << 16 | string body length << 4 | class, json_lane.h's
+// class numbers) and keeps ':' and ',' as tokens: tape_lines derives the grammar from each token's
+// two predecessors, not from a DFA state that a folded flag could advance.
 constexpr uint32_t T_NL = 12;
 constexpr uint32_t TAPE_CAP = 4096;  // tokens (16 KiB of LDS)
 
