@@ -119,7 +119,10 @@ def _types(pa, stats=True, parsed=None):
 def _parsed_struct(pa, pv, parsed, typ):
     """Cast(add.partitionValues[c] AS type) per partition column: a missing key or a failed
     non-ANSI cast is null (the device filter's cast grammar, predicates.cast_partition_value)."""
-    from .predicates import cast_partition_value
+    from .predicates import cast_partition_value, timestamp_micros
+
+    def cast(s, t):  # timestamps as microseconds: Arrow holds years a datetime cannot
+        return (None if s is None else timestamp_micros(s)) if t == "timestamp" else cast_partition_value(s, t)
     keys = pv.keys.to_pylist() if len(pv) else []
     items = pv.items.to_pylist() if len(pv) else []
     offs = pv.offsets.to_pylist() if len(pv) else [0]
@@ -128,7 +131,7 @@ def _parsed_struct(pa, pv, parsed, typ):
     for i in range(len(pv)):
         m = {} if nulls[i] else {keys[j]: items[j] for j in range(offs[i], offs[i + 1])}
         for c, t in parsed.items():
-            cols[c].append(cast_partition_value(m.get(c), t))
+            cols[c].append(cast(m.get(c), t))
     arrays = [pa.array(cols[c], f.type) for c, f in zip(parsed, typ)]
     return pa.StructArray.from_arrays(arrays, fields=list(typ))
 

@@ -3258,7 +3258,36 @@ static void build_export(dr_state& st, int which) {
 static const char* kPvKey = "add.partitionValues.key_value.key";
 static const char* kPvVal = "add.partitionValues.key_value.value";
 
-// Host validation of the postfix program: operand indices and stack discipline.
+// The types this PR's callers may compare: a column takes literals of its own type (a decimal's
+// precision and scale included), and a FLOAT column also a DOUBLE literal (the value is widened).
+// STRING, the integer kinds, DATE and BOOLEAN among themselves keep their old leniency (unchecked).
+static bool new_pred_type(int32_t t) { return (t & 0xff) >= DR_T_FLOAT; }
+static bool lit_fits(int32_t ctype, int32_t ltype) {
+  if (!new_pred_type(ctype) && !new_pred_type(ltype)) return true;
+  return ctype == ltype || (ctype == DR_T_FLOAT && ltype == DR_T_DOUBLE);
+}
+
+// A DECIMAL literal: 16 bytes, little-endian two's complement, in the string bytes.
+static void decimal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t* hi) {
+  uint64_t w[2];
+  std::memcpy(w, p.lit_str_bytes + p.lit_str_off[k], 16);
+  *lo = int64_t(w[0]);
+  *hi = int64_t(w[1]);
+}
+
+// Literal k as the evaluators compare it: FLOAT / DOUBLE as their order keys (fp_key32 / fp_key64,
+// the device's own functions), a DECIMAL's two words, everything else as given.
+static void literal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t* hi) {
+  *lo = p.lit_i64[k];
+  *hi = 0;
+  if (p.lit_null[k]) return;
+  const int base = p.lit_types[k] & 0xff;
+  if (base == DR_T_FLOAT) *lo = fp_key32(uint32_t(p.lit_i64[k]));
+  else if (base == DR_T_DOUBLE) *lo = fp_key64(uint64_t(p.lit_i64[k]));
+  else if (base == DR_T_DECIMAL) decimal_words(p, k, lo, hi);
+}
+
+// Host validation of the postfix program: types, literals, operand indices and stack discipline.
 static void check_program(const dr_predicate& p) {
   if (p.ncols < 0 || uint32_t(p.ncols) > filter_max_cols())
     fail(DR_E_UNSUPPORTED, fmt("at most %u partition columns per predicate", filter_max_cols()));
@@ -3266,9 +3295,31 @@ static void check_program(const dr_predicate& p) {
   if (p.ncols && (!p.col_names || !p.col_types)) fail(DR_E_INVALID_ARG, "missing partition columns");
   if (p.nlits && (!p.lit_types || !p.lit_i64 || !p.lit_null || !p.lit_str_off))
     fail(DR_E_INVALID_ARG, "missing literals");
+  // a type code: STRING .. BINARY bare, DECIMAL | p << 8 | s << 16 with 1 <= p <= 38, s <= p
+  auto type_ok = [](int32_t t) {
+    if (t < 0) return false;
+    if ((t & 0xff) != DR_T_DECIMAL) return t <= DR_T_BINARY;
+    const int32_t prec = (t >> 8) & 0xff, scale = t >> 16;
+    return prec >= 1 && prec <= 38 && scale <= prec;
+  };
   for (int32_t c = 0; c < p.ncols; ++c)
-    if (p.col_types[c] < DR_T_STRING || p.col_types[c] > DR_T_BOOLEAN || !p.col_names[c])
+    if (!type_ok(p.col_types[c]) || !p.col_names[c])
       fail(DR_E_UNSUPPORTED, "unsupported partition column type");
+  for (int32_t k = 0; k < p.nlits; ++k) {
+    if (p.lit_null[k]) continue;
+    const int32_t t = p.lit_types[k];
+    if (!type_ok(t)) fail(DR_E_INVALID_ARG, fmt("predicate literal %d has no valid type (code %d)", k, t));
+    if ((t & 0xff) != DR_T_DECIMAL) continue;
+    if (!p.lit_str_bytes || p.lit_str_off[k] < 0 || p.lit_str_off[k + 1] - p.lit_str_off[k] != 16)
+      fail(DR_E_INVALID_ARG, fmt("decimal literal %d must be 16 bytes (little-endian two's complement)", k));
+    int64_t lo, hi;
+    decimal_words(p, k, &lo, &hi);
+    const __int128 v = (__int128(hi) << 64) | __int128(uint64_t(lo));
+    unsigned __int128 lim = 1;
+    for (int32_t d = 0; d < ((t >> 8) & 0xff); ++d) lim *= 10;
+    if ((v < 0 ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v) >= lim)
+      fail(DR_E_INVALID_ARG, fmt("decimal literal %d does not fit precision %d", k, (t >> 8) & 0xff));
+  }
   // stack discipline: every op's operands are whole subtrees (postfix -> tree)
   std::vector<int32_t> stack;
   for (int32_t k = 0; k < p.nops; ++k) {
@@ -3296,6 +3347,21 @@ static void check_program(const dr_predicate& p) {
     }
     if (stack.size() < pops)
       fail(DR_E_INVALID_ARG, op == DR_OP_IN ? "predicate stack underflow (IN)" : "predicate stack underflow");
+    // a literal compared with a column must be of a kind the column takes (lit_fits)
+    auto fits = [&](int32_t ck, int32_t lk) {
+      if (p.ops[ck].opcode != DR_OP_COL || p.ops[lk].opcode != DR_OP_LIT) return;
+      const int32_t c = p.ops[ck].arg, l = p.ops[lk].arg;
+      if (!p.lit_null[l] && !lit_fits(p.col_types[c], p.lit_types[l]))
+        fail(DR_E_INVALID_ARG, fmt("predicate literal %d (type %d) does not fit partition column %s (type %d)", l,
+                                   p.lit_types[l], p.col_names[c], p.col_types[c]));
+    };
+    if (op >= DR_OP_EQ && op <= DR_OP_NSEQ) {
+      const int32_t x = stack[stack.size() - 2], y = stack.back();
+      fits(x, y);
+      fits(y, x);
+    } else if (op == DR_OP_IN) {
+      for (size_t q = 1; q < pops; ++q) fits(stack[stack.size() - pops], stack[stack.size() - pops + q]);
+    }
     stack.resize(stack.size() - pops);
     stack.push_back(k);
   }
@@ -3357,7 +3423,8 @@ static std::vector<int32_t> lower_program(const dr_predicate& p) {
 struct LeafPlan {
   std::vector<FilterLeaf> leaves;
   std::vector<int32_t> prog;
-  std::vector<int64_t> i64;        // literal slots
+  std::vector<int64_t> i64;        // literal slots (FLOAT / DOUBLE: order keys; DECIMAL: the low word)
+  std::vector<int64_t> i64hi;      // parallel: a DECIMAL's high word
   std::vector<std::string> str;
 };
 static bool leafify(const dr_predicate& p, LeafPlan& L) {
@@ -3374,13 +3441,27 @@ static bool leafify(const dr_predicate& p, LeafPlan& L) {
   }
   auto is_col = [&](int32_t k) { return p.ops[k].opcode == DR_OP_COL; };
   auto is_lit = [&](int32_t k) { return p.ops[k].opcode == DR_OP_LIT; };
-  auto kind_ok = [&](int32_t col, int32_t lit) {  // string columns with string literals, others numeric
-    return (p.col_types[col] == DR_T_STRING) == (p.lit_types[lit] == DR_T_STRING);
+  auto is_str = [](int32_t t) { return leaf_kind(t) == DR_T_STRING; };
+  // string (and binary) columns with literals of bytes, others numeric; the new types by lit_fits
+  auto kind_ok = [&](int32_t col, int32_t lit) {
+    return is_str(p.col_types[col]) == is_str(p.lit_types[lit]) && lit_fits(p.col_types[col], p.lit_types[lit]);
+  };
+  // a FLOAT column's literal as the leaf compares it: a DOUBLE literal's key as it is (the leaf widens
+  // the value, pad = 2), and then a FLOAT literal's key widened like the value
+  auto fp_word = [&](int32_t lit, bool widen) {
+    int64_t lo, hi;
+    literal_words(p, lit, &lo, &hi);
+    return widen && p.lit_types[lit] == DR_T_FLOAT ? fp_key_widen(lo) : lo;
   };
   auto slot = [&](int32_t lit) {
-    L.i64.push_back(p.lit_i64[lit]);
-    L.str.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[lit],
-                       size_t(p.lit_str_off[lit + 1] - p.lit_str_off[lit]));
+    int64_t lo, hi;
+    literal_words(p, lit, &lo, &hi);
+    L.i64.push_back(lo);
+    L.i64hi.push_back(hi);
+    if (is_str(p.lit_types[lit]))
+      L.str.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[lit],
+                         size_t(p.lit_str_off[lit + 1] - p.lit_str_off[lit]));
+    else L.str.emplace_back();
     return int32_t(L.i64.size() - 1);
   };
   int depth = 0, max_depth = 0;
@@ -3421,23 +3502,47 @@ static bool leafify(const dr_predicate& p, LeafPlan& L) {
           return false;
         }
         if (!p.lit_null[l] && !kind_ok(c, l)) return false;
-        return push_leaf(FilterLeaf{c, fop, slot(l), 0, p.lit_null[l] ? 1 : 0, 0});
+        const bool widen = !p.lit_null[l] && p.col_types[c] == DR_T_FLOAT && p.lit_types[l] == DR_T_DOUBLE;
+        return push_leaf(FilterLeaf{c, fop, slot(l), 0, p.lit_null[l] ? 1 : 0, widen ? 2 : 0});
       }
       case DR_OP_IN: {
         if (!is_col(ch[0])) return false;
         const int32_t c = p.ops[ch[0]].arg;
-        const bool str = p.col_types[c] == DR_T_STRING;
-        bool has_null = false;
+        const int kind = leaf_kind(p.col_types[c]);
+        const bool str = kind == DR_T_STRING;
+        bool has_null = false, widen = false;
         std::vector<int64_t> iv;
+        std::vector<std::pair<int64_t, uint64_t>> dv;  // decimals: (high signed, low unsigned)
         std::vector<std::string> sv;
+        for (size_t q = 1; q < ch.size(); ++q)  // a FLOAT column with a DOUBLE element: all in binary64
+          widen |= is_lit(ch[q]) && !p.lit_null[p.ops[ch[q]].arg] && p.col_types[c] == DR_T_FLOAT &&
+                   p.lit_types[p.ops[ch[q]].arg] == DR_T_DOUBLE;
         for (size_t q = 1; q < ch.size(); ++q) {
           if (!is_lit(ch[q])) return false;
           const int32_t l = p.ops[ch[q]].arg;
           if (p.lit_null[l]) { has_null = true; continue; }
           if (!kind_ok(c, l)) return false;
-          if (str) sv.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[l],
-                                   size_t(p.lit_str_off[l + 1] - p.lit_str_off[l]));
-          else iv.push_back(p.lit_i64[l]);
+          if (str) {
+            sv.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[l],
+                            size_t(p.lit_str_off[l + 1] - p.lit_str_off[l]));
+          } else if (kind == DR_T_DECIMAL) {
+            int64_t lo, hi;
+            literal_words(p, l, &lo, &hi);
+            dv.emplace_back(hi, uint64_t(lo));
+          } else {
+            iv.push_back(fp_word(l, widen));  // FLOAT / DOUBLE: the key, so the set is sorted by key
+          }
+        }
+        if (kind == DR_T_DECIMAL) {  // sorted as 128-bit values
+          std::sort(dv.begin(), dv.end());
+          dv.erase(std::unique(dv.begin(), dv.end()), dv.end());
+          const int32_t first = int32_t(L.i64.size());
+          for (const auto& d : dv) {
+            L.i64.push_back(int64_t(d.second));
+            L.i64hi.push_back(d.first);
+            L.str.emplace_back();
+          }
+          return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(dv.size()), has_null ? 1 : 0, 0});
         }
         std::sort(iv.begin(), iv.end());
         iv.erase(std::unique(iv.begin(), iv.end()), iv.end());
@@ -3447,7 +3552,8 @@ static bool leafify(const dr_predicate& p, LeafPlan& L) {
         const size_t m = str ? sv.size() : iv.size();
         // an integer set spanning < 2^16 values: a bitmap, one word read per file instead of a
         // binary search (pad = 1; literals [min, words, bits...])
-        if (!str && m >= 8 && uint64_t(iv.back()) - uint64_t(iv.front()) < 65536) {
+        const bool fp = kind == DR_T_FLOAT || kind == DR_T_DOUBLE;  // the bitmap: one-word integer kinds only
+        if (!str && !fp && m >= 8 && uint64_t(iv.back()) - uint64_t(iv.front()) < 65536) {
           const uint64_t span = uint64_t(iv.back()) - uint64_t(iv.front()) + 1, nw = (span + 63) / 64;
           std::vector<uint64_t> bits(nw, 0);
           for (int64_t x : iv) {
@@ -3457,14 +3563,16 @@ static bool leafify(const dr_predicate& p, LeafPlan& L) {
           L.i64.push_back(iv.front());
           L.i64.push_back(int64_t(nw));
           for (uint64_t w : bits) L.i64.push_back(int64_t(w));
+          L.i64hi.resize(L.i64.size(), 0);
           L.str.resize(L.i64.size());
           return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, 1});
         }
         for (size_t q = 0; q < m; ++q) {
           L.i64.push_back(str ? 0 : iv[q]);
+          L.i64hi.push_back(0);
           L.str.push_back(str ? sv[q] : std::string());
         }
-        return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, 0});
+        return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, widen ? 2 : 0});
       }
       default:
         return false;
@@ -4499,12 +4607,13 @@ static PvColumn pv_column(const dr_state::PvCol& c) {
 }
 
 // Dictionary-encodes a typed partition column (k_dict_*): abandoned (dict = 0) past DICT_MAX - 1
-// distinct values, for DECIMAL (two-word values) and on a string hash collision.
+// distinct values, for a DECIMAL of precision > 18 (two-word values: the key is the low word) and
+// on a string hash collision.
 static void build_dict(dr_state& st, dr_state::PvCol& col) {
   if (col.dict >= 0) return;
   col.dict = 0;
   const int base = col.type & 0xff;
-  if (base == DR_T_DECIMAL || !st.n_live) return;
+  if ((base == DR_T_DECIMAL && ((col.type >> 8) & 0xff) > 18) || !st.n_live) return;
   dr_ctx* ctx = st.ctx;
   hipStream_t stream = ctx->stream;
   const uint64_t n = st.n_live;
@@ -4598,7 +4707,8 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& pred)
       f.slot = -1;
       for (int32_t u = 0; u < la.nucol; ++u)
         if (la.ucol[u] == f.col) f.slot = u;
-      f.ctype = la.cols[f.col].type;
+      f.ctype = leaf_kind(la.cols[f.col].type);
+      la.extended |= f.ctype == DR_T_FLOAT || f.ctype == DR_T_DOUBLE || f.ctype == DR_T_DECIMAL;
     }
     const uint64_t ng = filter_leaf_groups(st.n_live);
     DBuf<uint64_t> mask(ctx, uint64_t(filter_leaf_mask_words()) * ng), wg_off(ctx, ng + 1);
@@ -4631,6 +4741,7 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& pred)
     };
     const size_t o_s8 = put(s8.data(), 8 * s8.size()), o_soff = put(soff.data(), 8 * soff.size());
     const size_t o_prog = put(lp.prog.data(), 4 * lp.prog.size()), o_i64 = put(lp.i64.data(), 8 * lp.i64.size());
+    const size_t o_hi = put(lp.i64hi.data(), 8 * lp.i64hi.size());
     const size_t o_leaves = put(lp.leaves.data(), sizeof(FilterLeaf) * lp.leaves.size());
     const size_t o_toff = put(tab_off.data(), 4 * tab_off.size()), o_sb = put(sbytes.data(), sbytes.size());
     DBuf<uint8_t> d_blob = upload(ctx, blob.data(), blob.size());
@@ -4638,6 +4749,7 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& pred)
     la.lit_str_off = reinterpret_cast<const uint64_t*>(d_blob.p + o_soff);
     la.prog = reinterpret_cast<const int32_t*>(d_blob.p + o_prog);
     la.lit_i64 = reinterpret_cast<const int64_t*>(d_blob.p + o_i64);
+    la.lit_hi = reinterpret_cast<const int64_t*>(d_blob.p + o_hi);
     la.leaves = reinterpret_cast<const FilterLeaf*>(d_blob.p + o_leaves);
     la.lit_str = d_blob.p + o_sb;
     const uint32_t* d_toff = reinterpret_cast<const uint32_t*>(d_blob.p + o_toff);
@@ -4655,6 +4767,7 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& pred)
       d.tab_off = d_toff;
       d.tab = d_tab.p;
       d.lit_i64 = la.lit_i64;
+      d.lit_hi = la.lit_hi;
       d.lit_s8 = la.lit_s8;
       d.lit_str_off = la.lit_str_off;
       d.lit_str = la.lit_str;
@@ -4691,7 +4804,9 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& pred)
   const uint64_t lit_bytes = pred.nlits ? lit_off[size_t(pred.nlits)] : 0;
   DBuf<int32_t> d_ops = upload(ctx, ops.data(), ops.size());
   DBuf<int32_t> d_lt = upload(ctx, pred.lit_types, size_t(pred.nlits));
-  DBuf<int64_t> d_li = upload(ctx, pred.lit_i64, size_t(pred.nlits));
+  std::vector<int64_t> lit_lo(size_t(pred.nlits)), lit_hi(size_t(pred.nlits));
+  for (int32_t k = 0; k < pred.nlits; ++k) literal_words(pred, k, &lit_lo[size_t(k)], &lit_hi[size_t(k)]);
+  DBuf<int64_t> d_li = upload(ctx, lit_lo.data(), lit_lo.size()), d_lh = upload(ctx, lit_hi.data(), lit_hi.size());
   DBuf<uint8_t> d_ln = upload(ctx, pred.lit_null, size_t(pred.nlits));
   DBuf<uint64_t> d_lo = upload(ctx, lit_off.data(), lit_off.size());
   DBuf<uint8_t> d_ls = upload(ctx, pred.lit_str_bytes, size_t(lit_bytes));
@@ -4699,6 +4814,7 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& pred)
   fa.ops = d_ops.p;
   fa.lit_types = d_lt.p;
   fa.lit_i64 = d_li.p;
+  fa.lit_hi = d_lh.p;
   fa.lit_null = d_ln.p;
   fa.lit_str_off = d_lo.p;
   fa.lit_str = d_ls.p;

@@ -112,11 +112,15 @@ __device__ __forceinline__ bool each_member(const uint8_t* p, const uint8_t* e, 
 }
 
 // ---- casts: Cast(string AS type), non-ANSI (failure -> NULL) ----------------------------------------
+// str: the value's kind -- 0 integer, 1 bytes (s, n), 2 / 3 a binary32 / binary64 order key
+// (fp_key32 / fp_key64), 4 a decimal (v unsigned under the signed high word hi)
+enum SvKind : uint8_t { SV_INT = 0, SV_STR = 1, SV_F32 = 2, SV_F64 = 3, SV_DEC = 4 };
 struct SV {
   int64_t v;
   const uint8_t* s;
   uint32_t n;
   uint8_t null, str;
+  int64_t hi;
 };
 
 __device__ __forceinline__ bool cast_ws(uint8_t c) {  // UTF8String.trim-like set of the restatement
@@ -219,8 +223,8 @@ __device__ bool parse_date(const uint8_t* s, uint32_t n, int64_t* out) {
 }
 
 // ---- casts of partitionValues_parsed's other types (D/Checkpoints.scala:380-388: Cast(pv AS type)) --
-// float / double, decimal(p, s), timestamp and binary partition columns. The K5 predicate program
-// does not take them (check_program); the checkpoint writer does.
+// float / double, decimal(p, s), timestamp and binary partition columns, for the checkpoint writer
+// and the K5 predicate program alike.
 __device__ __forceinline__ bool jws(uint8_t c) { return c <= ' '; }  // String.trim / UTF8String.trimAll
 
 // Double.parseDouble / Float.parseFloat of the trimmed text (Java's FloatingDecimal grammar: sign,
@@ -543,13 +547,21 @@ __device__ SV cast_value(const uint8_t* s, uint32_t n, bool present, int type) {
 }
 
 __device__ int cmp_sv(const SV& a, const SV& b) {
-  if (a.str && b.str) {
+  if (a.str == SV_STR && b.str == SV_STR) {
     const uint32_t m = a.n < b.n ? a.n : b.n;
     for (uint32_t k = 0; k < m; ++k)
       if (a.s[k] != b.s[k]) return a.s[k] < b.s[k] ? -1 : 1;
     return a.n == b.n ? 0 : (a.n < b.n ? -1 : 1);
   }
-  return a.v == b.v ? 0 : (a.v < b.v ? -1 : 1);
+  if (a.str == SV_DEC && b.str == SV_DEC) {  // signed 128 bits: high word signed, low word unsigned
+    if (a.hi != b.hi) return a.hi < b.hi ? -1 : 1;
+    const uint64_t x = uint64_t(a.v), y = uint64_t(b.v);
+    return x == y ? 0 : (x < y ? -1 : 1);
+  }
+  // a binary32 value against a binary64 one: widened exactly first
+  const int64_t x = (a.str == SV_F32 && b.str == SV_F64) ? fp_key_widen(a.v) : a.v;
+  const int64_t y = (b.str == SV_F32 && a.str == SV_F64) ? fp_key_widen(b.v) : b.v;
+  return x == y ? 0 : (x < y ? -1 : 1);
 }
 
 constexpr int PV_STACK = 32;
@@ -686,17 +698,31 @@ __global__ void __launch_bounds__(256) k_pv_extract(PvExtractArgs a) {
 }
 
 // ---- k_filter_typed ------------------------------------------------------------------------------
+// One non-string cache value as the evaluators compare it (kind = leaf_kind(col.type), uniform):
+// LONG / TIMESTAMP and a DECIMAL's low word as stored, DOUBLE / FLOAT as their order keys, the
+// 32-bit integer kinds sign-extended.
+__device__ __forceinline__ int64_t leaf_typed_value(const PvColumn& col, int kind, uint64_t i) {
+  if (kind == DR_T_LONG || kind == DR_T_DECIMAL) return col.w64[i];
+  if (kind == DR_T_DOUBLE) return fp_key64(uint64_t(col.w64[i]));
+  const uint32_t w = col.w32[i];
+  return kind == DR_T_FLOAT ? fp_key32(w) : int64_t(int32_t(w));
+}
+
 __device__ __forceinline__ SV load_col(const PvColumn& col, uint64_t i) {
   SV r{0, nullptr, 0, col.isnull[i], 0};
   if (r.null) return r;
-  if (col.type == DR_T_STRING) {
-    r.str = 1;
+  const int kind = leaf_kind(col.type);
+  if (kind == DR_T_STRING) {
+    r.str = SV_STR;
     r.s = reinterpret_cast<const uint8_t*>(col.sptr[i]);
     r.n = col.slen[i];
-  } else if (col.type == DR_T_LONG) {
+  } else if (kind == DR_T_DECIMAL) {
+    r.str = SV_DEC;
     r.v = col.w64[i];
+    r.hi = col.w64hi[i];
   } else {
-    r.v = int64_t(int32_t(col.w32[i]));
+    r.v = leaf_typed_value(col, kind, i);
+    r.str = kind == DR_T_FLOAT ? SV_F32 : kind == DR_T_DOUBLE ? SV_F64 : SV_INT;
   }
   return r;
 }
@@ -718,12 +744,15 @@ __global__ void __launch_bounds__(256) k_filter_typed(FilterTypedArgs a) {
         SV v{0, nullptr, 0, 1, 0};
         if (!a.lit_null[arg]) {
           v.null = 0;
-          if (a.lit_types[arg] == DR_T_STRING) {
-            v.str = 1;
+          const int kind = leaf_kind(a.lit_types[arg]);
+          if (kind == DR_T_STRING) {
+            v.str = SV_STR;
             v.s = a.lit_str + a.lit_str_off[arg];
             v.n = uint32_t(a.lit_str_off[arg + 1] - a.lit_str_off[arg]);
           } else {
             v.v = a.lit_i64[arg];
+            v.hi = a.lit_hi[arg];
+            v.str = kind == DR_T_FLOAT ? SV_F32 : kind == DR_T_DOUBLE ? SV_F64 : kind == DR_T_DECIMAL ? SV_DEC : SV_INT;
           }
         }
         st[sp++] = v;
@@ -816,66 +845,6 @@ __device__ __forceinline__ int bytes_cmp(const uint8_t* a, uint32_t an, const ui
   return an == bn ? 0 : (an < bn ? -1 : 1);
 }
 
-__device__ __forceinline__ uint32_t eval_leaf(const FilterLeafArgs& a, const FilterLeaf& L, uint64_t i,
-                                              const int64_t* lit_i64, const uint64_t* lit_s8) {
-  const PvColumn& col = a.cols[L.col];
-  const bool vnull = col.isnull[i] != 0;
-  if (L.op == DR_OP_ISNULL) return vnull ? 1u : 0u;
-  if (L.op == DR_OP_ISNOTNULL) return vnull ? 0u : 1u;
-  if (L.op == DR_OP_NSEQ && (vnull || L.lit_null)) return (vnull && L.lit_null) ? 1u : 0u;
-  if (L.op != DR_OP_IN && L.lit_null) return 2u;
-  if (vnull) return 2u;
-  const bool str = col.type == DR_T_STRING;
-  uint32_t vn = 0;
-  uint64_t v8 = 0;
-  int64_t v = 0;
-  if (str) {
-    vn = col.slen[i];
-    v8 = col.s8[i];
-  } else {
-    v = col.type == DR_T_LONG ? col.w64[i] : int64_t(int32_t(col.w32[i]));
-  }
-  // strings: the big-endian 8-byte prefixes order like the bytes; equal prefixes of two values of
-  // at most 8 bytes leave only the lengths; otherwise the value bytes are gathered
-  auto cmp_lit = [&](int32_t k) -> int {
-    if (str) {
-      const uint64_t o = a.lit_str_off[k];
-      const uint32_t ln = uint32_t(a.lit_str_off[k + 1] - o);
-      const uint64_t l8 = lit_s8[k];
-      if (v8 != l8) return v8 < l8 ? -1 : 1;
-      if (vn <= 8 && ln <= 8) return vn == ln ? 0 : (vn < ln ? -1 : 1);
-      return bytes_cmp(reinterpret_cast<const uint8_t*>(col.sptr[i]), vn, a.lit_str + o, ln);
-    }
-    const int64_t x = lit_i64[k];
-    return v == x ? 0 : (v < x ? -1 : 1);
-  };
-  if (L.op == DR_OP_IN && L.pad == 1) {  // an integer set as a bitmap over [min, min + 64 * words)
-    const uint64_t d = uint64_t(v) - uint64_t(lit_i64[L.lit]);
-    const uint64_t nbits = uint64_t(lit_i64[L.lit + 1]) * 64;
-    if (d < nbits && ((uint64_t(lit_i64[L.lit + 2 + (d >> 6)]) >> (d & 63)) & 1u)) return 1u;
-    return L.lit_null ? 2u : 0u;
-  }
-  if (L.op == DR_OP_IN) {  // binary search of the sorted set
-    int32_t lo = L.lit, hi = L.lit + L.nlit;
-    while (lo < hi) {
-      const int32_t mid = (lo + hi) >> 1;
-      const int c = cmp_lit(mid);
-      if (c == 0) return 1u;
-      if (c > 0) lo = mid + 1; else hi = mid;
-    }
-    return L.lit_null ? 2u : 0u;
-  }
-  const int c = cmp_lit(L.lit);
-  switch (L.op) {
-    case DR_OP_EQ: case DR_OP_NSEQ: return c == 0;
-    case DR_OP_NE: return c != 0;
-    case DR_OP_LT: return c < 0;
-    case DR_OP_LE: return c <= 0;
-    case DR_OP_GT: return c > 0;
-    default: return c >= 0;
-  }
-}
-
 // Four files per thread, strided by the workgroup (each load instruction of a wave reads 64
 // consecutive files): a leaf's column loads for all four are issued before any is compared, so one
 // round trip serves four files. The result leaves as bits -- one 64-bit mask per 64 files, in file
@@ -893,17 +862,23 @@ constexpr uint32_t FL_FILES = FL_T * FL_PER;  // files per tile (4 FL_PER mask w
 // The leaf result from a column value already in registers (nul, v = integer or big-endian 8-byte
 // string prefix, vn = string length); the long-string gather reads the column by file ordinal i.
 // The literals are the workgroup's LDS copies (li: integers and IN sets, ls8 / lso: the string
-// literals' prefixes and offsets).
+// literals' prefixes and offsets). X: the leaf may be of a FLOAT / DOUBLE / DECIMAL column (the
+// kernels for the older types are instantiated without that code: k_filter_leaf is register-tuned).
+template <bool X>
 __device__ __forceinline__ uint32_t leaf_value(const uint8_t* lit_str, const FilterLeaf& L, const PvColumn& col,
                                                uint64_t i, uint32_t nul, int64_t v, uint32_t vn, const int64_t* li,
-                                               const uint64_t* ls8, const uint64_t* lso) {
-  const bool str = L.ctype == DR_T_STRING;
+                                               const uint64_t* ls8, const uint64_t* lso, const int64_t* lhi) {
+  const bool str = L.ctype == DR_T_STRING, dec = X && L.ctype == DR_T_DECIMAL;
   const bool vnull = nul != 0;
   if (L.op == DR_OP_ISNULL) return vnull ? 1u : 0u;
   if (L.op == DR_OP_ISNOTNULL) return vnull ? 0u : 1u;
   if (L.op == DR_OP_NSEQ && (vnull || L.lit_null)) return (vnull && L.lit_null) ? 1u : 0u;
   if (L.op != DR_OP_IN && L.lit_null) return 2u;
   if (vnull) return 2u;
+  if (X && L.pad == 2) v = fp_key_widen(v);  // uniform: a FLOAT column against DOUBLE literals
+  // a decimal's high word: loaded here, for decimal leaves only and non-NULL values only (a NULL
+  // stands for the files past the end of a partial tile too), lhi[] read from global memory
+  const int64_t vh = dec ? col.w64hi[i] : 0;
   const uint64_t v8 = uint64_t(v);
   auto cmp_lit = [&](int32_t k) -> int {
     if (str) {
@@ -913,6 +888,12 @@ __device__ __forceinline__ uint32_t leaf_value(const uint8_t* lit_str, const Fil
       if (v8 != l8) return v8 < l8 ? -1 : 1;
       if (vn <= 8 && ln <= 8) return vn == ln ? 0 : (vn < ln ? -1 : 1);
       return bytes_cmp(reinterpret_cast<const uint8_t*>(col.sptr[i]), vn, lit_str + o, ln);
+    }
+    if (dec) {  // signed 128 bits: high word signed, low word unsigned
+      const int64_t xh = lhi[k];
+      const uint64_t xl = uint64_t(li[k]);
+      if (vh != xh) return vh < xh ? -1 : 1;
+      return v8 == xl ? 0 : (v8 < xl ? -1 : 1);
     }
     const int64_t x = li[k];
     return v == x ? 0 : (v < x ? -1 : 1);
@@ -947,10 +928,12 @@ __device__ __forceinline__ uint32_t leaf_value(const uint8_t* lit_str, const Fil
 // One column's values of a thread's FL_PER files (strided by the workgroup: each load instruction
 // of a wave reads 64 consecutive files; all loads in flight before any is used). The tile's base is
 // folded into uniform column pointers, so every load is a scalar base plus a 32-bit lane offset.
+template <bool X>
 __device__ __forceinline__ void load_col4(const FilterLeafArgs& a, const PvColumn& col, int ctype, uint64_t base,
                                           bool full, uint32_t (&nul)[FL_PER], uint32_t (&vn)[FL_PER],
                                           int64_t (&v)[FL_PER]) {
-  const bool str = ctype == DR_T_STRING, lng = ctype == DR_T_LONG;  // uniform
+  const bool str = ctype == DR_T_STRING, lng = ctype == DR_T_LONG || (X && ctype == DR_T_DECIMAL);  // uniform
+  const bool dbl = X && ctype == DR_T_DOUBLE, flt = X && ctype == DR_T_FLOAT;
   const uint8_t* pn = col.isnull + base;
 #pragma unroll
   for (int j = 0; j < FL_PER; ++j) {
@@ -964,6 +947,10 @@ __device__ __forceinline__ void load_col4(const FilterLeafArgs& a, const PvColum
       v[j] = ok ? int64_t(col.s8[base + o]) : 0;
     } else if (lng) {
       v[j] = ok ? col.w64[base + o] : 0;
+    } else if (dbl) {
+      v[j] = ok ? fp_key64(uint64_t(col.w64[base + o])) : 0;
+    } else if (flt) {
+      v[j] = ok ? fp_key32(col.w32[base + o]) : 0;
     } else {
       v[j] = ok ? int64_t(int32_t(col.w32[base + o])) : 0;
     }
@@ -980,7 +967,8 @@ __device__ __forceinline__ void load_col4(const FilterLeafArgs& a, const PvColum
 // otherwise each leaf loads its own column. A wave adds its selected count to its tile's (zeroed)
 // count: no barrier per tile.
 constexpr int FL_MAXPROG = 128, FL_MAXLEAF = 64, FL_MAXI64 = 1024, FL_MAXSTR = 256;
-__global__ void __launch_bounds__(FL_T) k_filter_leaf(FilterLeafArgs a) {
+template <bool X>
+__device__ __forceinline__ void filter_leaf_tiles(const FilterLeafArgs& a) {
   __shared__ int32_t sprog[2 * FL_MAXPROG];
   __shared__ FilterLeaf sleaf[FL_MAXLEAF];
   __shared__ int64_t slit[FL_MAXI64];
@@ -1006,7 +994,7 @@ __global__ void __launch_bounds__(FL_T) k_filter_leaf(FilterLeafArgs a) {
     for (int u = 0; u < FL_UCOLS; ++u) {
       if (u >= nu) break;  // uniform
       const PvColumn& col = a.cols[a.ucol[u]];
-      load_col4(a, col, col.type, base, full, cn[u], cl[u], cv[u]);
+      load_col4<X>(a, col, leaf_kind(col.type), base, full, cn[u], cl[u], cv[u]);
     }
     uint64_t stk[FL_PER];  // per file: 2 bits per entry, top at the low end
 #pragma unroll
@@ -1038,12 +1026,13 @@ __global__ void __launch_bounds__(FL_T) k_filter_leaf(FilterLeafArgs a) {
               if (u == L.slot) { n0[j] = cn[u][j]; l0[j] = cl[u][j]; v0[j] = cv[u][j]; }
           }
         } else {
-          load_col4(a, col, L.ctype, base, full, n0, l0, v0);
+          load_col4<X>(a, col, L.ctype, base, full, n0, l0, v0);
         }
 #pragma unroll
         for (int j = 0; j < FL_PER; ++j)
           stk[j] = (stk[j] << 2) |
-                   leaf_value(a.lit_str, L, col, base + threadIdx.x + uint64_t(j) * FL_T, n0[j], v0[j], l0[j], slit, ss8, ssoff);
+                   leaf_value<X>(a.lit_str, L, col, base + threadIdx.x + uint64_t(j) * FL_T, n0[j], v0[j], l0[j], slit, ss8, ssoff,
+                              a.lit_hi);
       } else if (op == LEAF_OP_NOT) {
 #pragma unroll
         for (int j = 0; j < FL_PER; ++j) {
@@ -1072,6 +1061,11 @@ __global__ void __launch_bounds__(FL_T) k_filter_leaf(FilterLeafArgs a) {
     if (lane == 0 && cnt) atomicAdd(&a.wg_count[tile], cnt);
   }
 }
+// k_filter_leaf: programs over STRING / BINARY, the integer kinds, DATE, BOOLEAN and TIMESTAMP
+// columns, exactly the code it was before the other types; k_filter_leaf_x: programs with a leaf
+// over a FLOAT, DOUBLE or DECIMAL column (FilterLeafArgs::extended, set by the host).
+__global__ void __launch_bounds__(FL_T) k_filter_leaf(FilterLeafArgs a) { filter_leaf_tiles<false>(a); }
+__global__ void __launch_bounds__(FL_T) k_filter_leaf_x(FilterLeafArgs a) { filter_leaf_tiles<true>(a); }
 
 // ---- K5 dictionary path ----------------------------------------------------------------------------
 // Partition columns are low-cardinality by construction (one value per directory), so the typed
@@ -1081,7 +1075,10 @@ __global__ void __launch_bounds__(FL_T) k_filter_leaf(FilterLeafArgs a) {
 // reads 2 bytes per file and column and looks the leaf results up in LDS (r04: the typed pass read
 // 28 B per file in nine loads and evaluated every leaf per file: 1.93 ms for 100M files).
 // Keys: the integer value itself (exact), or a string's xxh64 (k_dict_verify compares every file's
-// bytes with its code's representative, so a hash collision abandons the dictionary).
+// bytes with its code's representative, so a hash collision abandons the dictionary). FLOAT / DOUBLE:
+// the raw bits (0.0 and -0.0 are two codes whose leaves agree); TIMESTAMP: the microseconds; BINARY:
+// as a string; DECIMAL of precision <= 18: the low word, which is the whole value (wider ones keep
+// to the typed leaf kernel, engine.hip build_dict).
 __device__ __forceinline__ uint64_t dict_mix(uint64_t k) {
   k ^= k >> 33;
   k *= 0xff51afd7ed558ccdull;
@@ -1208,10 +1205,12 @@ __global__ void __launch_bounds__(256) k_dict_leaf(DictLeafArgs a, uint32_t tota
       vn = col.slen[row];
       v = int64_t(col.s8[row]);
     } else {
-      v = L.ctype == DR_T_LONG ? col.w64[row] : int64_t(int32_t(col.w32[row]));
+      v = leaf_typed_value(col, L.ctype, row);
     }
   }
-  a.tab[t] = uint8_t(leaf_value(a.lit_str, L, col, row, nul, v, vn, a.lit_i64, a.lit_s8, a.lit_str_off));
+  // X = true whatever the column: one thread per (leaf, code) has no register budget to keep, and a
+  // decimal(p <= 18) leaf reads w64hi[row] (allocated for every decimal; row is a live file) and lit_hi
+  a.tab[t] = uint8_t(leaf_value<true>(a.lit_str, L, col, row, nul, v, vn, a.lit_i64, a.lit_s8, a.lit_str_off, a.lit_hi));
 }
 
 // The per-file pass over codes: tiles of FL_FILES files, FL_PER per lane; every leaf is one LDS
@@ -1420,10 +1419,12 @@ uint32_t filter_leaf_mask_words() { return dev::FL_FILES / 64; }
 void launch_filter_leaf(const FilterLeafArgs& a, hipStream_t st) {
   if (a.nprog > dev::FL_MAXPROG || a.nleaves > dev::FL_MAXLEAF)
     throw std::runtime_error("filter program too long for the leaf kernel");
-  // persistent: four resident workgroups per CU (119 VGPRs: 4 waves/SIMD), each walking tiles grid-stride
+  // persistent: four resident workgroups per CU (k_filter_leaf 124 VGPRs: 4 waves/SIMD; k_filter_leaf_x 129: 3), each walking tiles grid-stride
   const unsigned g = unsigned(DR_FL_GRID ? std::min<uint64_t>(filter_leaf_groups(a.n_live), 256 * DR_FL_GRID)
                                           : filter_leaf_groups(a.n_live));
-  if (a.n_live) DR_LAUNCH(dev::k_filter_leaf, dim3(g), dim3(dev::FL_T), 0, st, a);
+  if (!a.n_live) return;
+  if (a.extended) DR_LAUNCH(dev::k_filter_leaf_x, dim3(g), dim3(dev::FL_T), 0, st, a);
+  else DR_LAUNCH(dev::k_filter_leaf, dim3(g), dim3(dev::FL_T), 0, st, a);
 }
 uint32_t filter_leaf_max_prog() { return dev::FL_MAXPROG; }
 void launch_dict_insert(const PvDictArgs& a, hipStream_t st) {

@@ -12,7 +12,15 @@ Mirrors the reference's metadata-predicate handling:
 Expressions are nested tuples (the oracle's format): ("col", name), ("lit", type, value),
 (op, a, b) for = != < <= > >= <=>, ("in", a, [lits]), ("isnull", a), ("isnotnull", a),
 ("and", a, b), ("or", a, b), ("not", a). Types: "string", "byte", "short", "integer", "long",
-"date", "boolean". The program is evaluated on the GPU; nothing here evaluates it.
+"date", "boolean", "float", "double", "timestamp", "binary", "decimal(p,s)" ("decimal" is
+decimal(10,0)). The program is evaluated on the GPU; nothing here evaluates it.
+
+Literal values of the later types: "double" a float; "float" a float that binary32 holds exactly;
+"timestamp" microseconds since the epoch as an int (a datetime, or a string in the partition
+values' own grammar, is converted); "decimal(p,s)" the unscaled int at scale s (a decimal.Decimal
+that quantises to s exactly is converted); "binary" bytes. A column takes literals of its own type,
+and a float column also a double literal (Catalyst's `floatcol > 1.5`); anything else among these
+types is a PredicateError -- widening, between decimal types too, is the caller's.
 """
 from __future__ import annotations
 
@@ -20,12 +28,27 @@ import ctypes as C
 import datetime as _dt
 import json
 import re
+import struct
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 from . import _native as N
 
-TYPE_CODE = {"string": 0, "byte": 1, "short": 2, "integer": 3, "long": 4, "date": 5, "boolean": 6}
+TYPE_CODE = {"string": 0, "byte": 1, "short": 2, "integer": 3, "long": 4, "date": 5, "boolean": 6,
+             "float": 7, "double": 8, "timestamp": 9, "binary": 10, "decimal": 11 | 10 << 8}
+T_FLOAT, T_DOUBLE, T_TIMESTAMP, T_BINARY, T_DECIMAL = 7, 8, 9, 10, 11
+_DECIMAL_RE = re.compile(r"decimal\((\d+),(\d+)\)")
+
+
+def type_code(typ: str) -> Optional[int]:
+    """dr_pred_type of a Spark type name (a decimal's code carries p << 8 | s << 16); None when the
+    predicate program has no such type."""
+    if typ in TYPE_CODE:
+        return TYPE_CODE[typ]
+    m = _DECIMAL_RE.fullmatch(typ) if isinstance(typ, str) else None
+    if m and 1 <= int(m.group(1)) <= 38 and int(m.group(2)) <= int(m.group(1)):
+        return T_DECIMAL | int(m.group(1)) << 8 | int(m.group(2)) << 16
+    return None
 OP_COL, OP_LIT = 0, 1
 OP_CODE = {"=": 2, "!=": 3, "<": 4, "<=": 5, ">": 6, ">=": 7, "<=>": 8, "in": 9, "isnull": 10,
            "isnotnull": 11, "and": 12, "or": 13, "not": 14}
@@ -120,7 +143,10 @@ def cast_partition_value(s: Optional[str], typ: str):
     """Cast(Literal(partitionValues(col)), partition type) on the host, non-ANSI (a failed cast is
     null), as TahoeFileIndex.listFiles builds a partition row (D/files/TahoeFileIndex.scala:61-64):
     integral types from trimmed decimal text in range, booleans from t/true/y/yes/1 and
-    f/false/n/no/0, dates as datetime.date, strings unchanged. Same grammar as the device cast."""
+    f/false/n/no/0, dates as datetime.date, strings unchanged. Same grammar as the device cast.
+    Timestamps are UTC datetimes; one whose year datetime cannot hold (outside 1..9999, which Spark
+    and the device accept) is its microseconds since the epoch as an int, never None: a file that
+    dr_filter selects by such a value keeps a non-NULL group row in Snapshot.list_files."""
     if s is None:
         return None
     if typ == "string":
@@ -143,7 +169,12 @@ def cast_partition_value(s: Optional[str], typ: str):
         return s.encode("utf-8")
     if typ == "timestamp":
         us = timestamp_micros(s)
-        return None if us is None else _dt.datetime(1970, 1, 1, tzinfo=_dt.timezone.utc) + _dt.timedelta(microseconds=us)
+        if us is None:
+            return None
+        try:
+            return _dt.datetime(1970, 1, 1, tzinfo=_dt.timezone.utc) + _dt.timedelta(microseconds=us)
+        except OverflowError:  # a year outside datetime's 1..9999: the microseconds themselves
+            return us
     dm = re.fullmatch(r"decimal(?:\((\d+),(\d+)\))?", typ)
     if dm:
         p, sc = (int(dm.group(1)), int(dm.group(2))) if dm.group(1) else (10, 0)
@@ -240,6 +271,18 @@ _TS_RE = re.compile(r"([+-]?)(\d{4,6})(?:-(\d{1,2})(?:-(\d{1,2})(?:[ T](\d{1,2})
 _TZ_RE = re.compile(r"(?:Z|(?:UTC|GMT|UT)?(?:([+-])(\d{1,2})(?::?(\d{1,2})(?::?(\d{1,2}))?)?)?)")
 
 
+def _days_from_civil(y: int, mo: int, d: int) -> Optional[int]:
+    """Days since 1970-01-01 of a proleptic Gregorian date (java.time.LocalDate, which Spark uses),
+    for any year -- datetime.date stops at 1..9999 and the device does not; None for no such date."""
+    leap = (y % 4 == 0 and y % 100 != 0) or y % 400 == 0
+    if not 1 <= mo <= 12 or not 1 <= d <= (31, 29 if leap else 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)[mo - 1]:
+        return None
+    y -= mo <= 2
+    era, yoe = divmod(y, 400)
+    doy = (153 * (mo + (-3 if mo > 2 else 9)) + 2) // 5 + d - 1
+    return era * 146097 + yoe * 365 + yoe // 4 - yoe // 100 + doy - 719468
+
+
 def timestamp_micros(s: str) -> Optional[int]:
     """DateTimeUtils.stringToTimestamp with the session zone UTC, the subset the device reads."""
     t = _jtrim(s)
@@ -247,10 +290,8 @@ def timestamp_micros(s: str) -> Optional[int]:
     if not m:
         return None
     sign, y, mo, d, hh, mi, ss, frac, zone = m.groups()
-    y = int(y) * (-1 if sign == "-" else 1)
-    try:
-        day = (_dt.date(y, int(mo or 1), int(d or 1)) - _EPOCH).days
-    except ValueError:
+    day = _days_from_civil(int(y) * (-1 if sign == "-" else 1), int(mo or 1), int(d or 1))
+    if day is None:
         return None
     hh, mi, ss = int(hh or 0), int(mi or 0), int(ss or 0)
     if hh > 23 or mi > 59 or ss > 59:
@@ -269,13 +310,96 @@ def timestamp_micros(s: str) -> Optional[int]:
     return ((day * 86400 + hh * 3600 + mi * 60 + ss) - off) * 1_000_000 + us
 
 
+def double_bits(x: float) -> int:
+    """The binary64 bits of x."""
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+def float_bits(x: float) -> int:
+    """The binary32 bits of x; PredicateError unless binary32 holds x exactly."""
+    try:
+        b = struct.pack("<f", x)
+    except OverflowError:
+        raise PredicateError("float literal %r is not a binary32 value" % (x,))
+    if x == x and struct.unpack("<f", b)[0] != x:
+        raise PredicateError("float literal %r is not a binary32 value" % (x,))
+    return struct.unpack("<I", b)[0]
+
+
+def fp_order_key(bits: int, width: int = 64) -> int:
+    """The device's floating-point order key (fp_key64 / fp_key32 of csrc/kernels.h) of a value's
+    bits: every NaN canonical, -0.0 as +0.0, then the magnitude bits of negative values flipped.
+    The signed integer order of the keys is SQLOrderingUtil.compareDoubles / compareFloats
+    (-0.0 = 0.0, NaN = NaN, NaN above +Infinity)."""
+    mag = (1 << (width - 1)) - 1
+    inf, qnan = (0x7ff0000000000000, 0x7ff8000000000000) if width == 64 else (0x7f800000, 0x7fc00000)
+    if bits & mag > inf:
+        bits = qnan
+    if bits == 1 << (width - 1):
+        bits = 0
+    k = bits - (1 << width) if bits >> (width - 1) else bits
+    return k ^ mag if k < 0 else k
+
+
+def decimal_bytes(unscaled: int) -> bytes:
+    """A decimal literal's wire form: the unscaled value as 16 bytes, little-endian two's complement."""
+    return int(unscaled).to_bytes(16, "little", signed=True)
+
+
+def _decimal_unscaled(v, p: int, s: int) -> int:
+    import decimal
+    if isinstance(v, decimal.Decimal):
+        ctx = decimal.Context(prec=200)
+        u = v.scaleb(s, context=ctx) if v.is_finite() else None
+        if u is None or u != u.to_integral_value(context=ctx):
+            raise PredicateError("decimal literal %s does not quantise to scale %d exactly" % (v, s))
+        u = int(u)
+    elif isinstance(v, int) and not isinstance(v, bool):
+        u = v
+    else:
+        raise PredicateError("decimal literal %r: the unscaled int or a decimal.Decimal expected" % (v,))
+    if abs(u) >= 10 ** p:
+        raise PredicateError("decimal literal %r does not fit precision %d" % (v, p))
+    return u
+
+
+def _timestamp_lit(v) -> int:
+    if isinstance(v, str):
+        us = timestamp_micros(v)
+        if us is None:
+            raise PredicateError("bad timestamp literal %r" % v)
+        return us
+    if isinstance(v, _dt.datetime):
+        if v.tzinfo is None:  # the session zone: UTC
+            v = v.replace(tzinfo=_dt.timezone.utc)
+        d = v - _dt.datetime(1970, 1, 1, tzinfo=_dt.timezone.utc)
+        return (d.days * 86400 + d.seconds) * 1_000_000 + d.microseconds
+    if isinstance(v, int) and not isinstance(v, bool):
+        return v
+    raise PredicateError("bad timestamp literal %r" % (v,))
+
+
 def _lit(typ: str, v):
     """Literal value as the device sees it (the oracle's _lit_value): dates as days since the
-    epoch, booleans as 0/1, strings as bytes."""
-    if typ not in TYPE_CODE:
+    epoch, booleans as 0/1, strings and binaries as bytes, floats and doubles as their bits,
+    timestamps as microseconds, decimals as their 16 bytes."""
+    code = type_code(typ)
+    if code is None:
         raise PredicateError("unsupported literal type %r" % typ)
     if v is None:
         return None
+    if code in (T_FLOAT, T_DOUBLE):
+        if isinstance(v, bool) or not isinstance(v, (float, int)) or float(v) != v and v == v:
+            raise PredicateError("%s literal %r: a float expected" % (typ, v))
+        return float_bits(float(v)) if code == T_FLOAT else double_bits(float(v))
+    if code == T_TIMESTAMP:
+        return _timestamp_lit(v)
+    if code == T_BINARY:
+        if not isinstance(v, (bytes, bytearray)):
+            raise PredicateError("binary literal %r: bytes expected" % (v,))
+        return bytes(v)
+    if code & 0xff == T_DECIMAL:
+        return decimal_bytes(_decimal_unscaled(v, (code >> 8) & 0xff, code >> 16))
     if typ == "date":
         if isinstance(v, str):
             days = _date_days(v)
@@ -305,16 +429,28 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
         if exact is None:
             raise PredicateError("%s is not a partition column" % name)
         typ = schema[exact]
-        if typ not in TYPE_CODE:
+        if type_code(typ) is None:
             raise PredicateError("partition column %s has unsupported type %s" % (exact, typ))
         if exact not in colidx:
             colidx[exact] = len(p.cols)
-            p.cols.append((exact, TYPE_CODE[typ]))
+            p.cols.append((exact, type_code(typ)))
         p.ops.append((OP_COL, colidx[exact]))
 
     def lit(typ, v):
-        p.lits.append((TYPE_CODE[typ], _lit(typ, v)))
+        value = _lit(typ, v)
+        p.lits.append((type_code(typ), value))
         p.ops.append((OP_LIT, len(p.lits) - 1))
+
+    def fits(a, b):
+        """A literal compared with a column is of a kind the column takes (dr_filter's own rule)."""
+        if a[0] != "col" or b[0] != "lit" or b[2] is None:
+            return
+        exact = _resolve(a[1], parts)
+        ct, lt = type_code(schema[exact]) if exact is not None else None, type_code(b[1])
+        if ct is None or lt is None:
+            return  # reported by col() / lit()
+        if (ct & 0xff >= T_FLOAT or lt & 0xff >= T_FLOAT) and not (ct == lt or (ct == T_FLOAT and lt == T_DOUBLE)):
+            raise PredicateError("a %s literal does not fit partition column %s of type %s" % (b[1], exact, schema[exact]))
 
     def emit(e):
         op = e[0]
@@ -325,12 +461,16 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
         elif op == "in":
             emit(e[1])
             for l in e[2]:
+                fits(e[1], l)
                 emit(l)
             p.ops.append((OP_CODE["in"], len(e[2])))
         elif op in ("isnull", "isnotnull", "not"):
             emit(e[1])
             p.ops.append((OP_CODE[op], 0))
         elif op in OP_CODE:
+            if op not in ("and", "or"):
+                fits(e[1], e[2])
+                fits(e[2], e[1])
             emit(e[1])
             emit(e[2])
             p.ops.append((OP_CODE[op], 0))
@@ -373,7 +513,7 @@ def lower_program(prog: Program):
         elif isinstance(v, bytes):
             blob += v
         else:
-            li[i] = int(v)
+            li[i] = int(v) - (1 << 64) if int(v) >= 1 << 63 else int(v)  # a double's bits as int64
     lo[nl] = len(blob)
     lb = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob + b"\0")
     keep += [ops, names, ctypes_, lt, li, ln, lo, lb]

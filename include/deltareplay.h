@@ -37,7 +37,11 @@ extern "C" {
  *      shared by threads; a range outlives its context
  *      added within ABI 4 (no existing entry point changed; a host that wants it looks the symbol up
  *      and does without when it is absent): dr_state_export_rows; dr_state_lookup_paths with
- *      DR_OPT_LOOKUP_KEY_BITS */
+ *      DR_OPT_LOOKUP_KEY_BITS
+ *      also within ABI 4, no signature or struct changed: dr_filter takes partition columns and literals
+ *      of DR_T_FLOAT .. DR_T_DECIMAL (encodings at dr_pred_type). A library from before answers
+ *      DR_E_UNSUPPORTED ("unsupported partition column type") for such a column, as it always did; the
+ *      host then keeps that conjunct on its own side */
 #define DR_ABI_VERSION 4
 
 /* Status codes. The JNI shim rethrows the reference's exception class with dr_last_error():
@@ -403,12 +407,31 @@ int dr_parsed_release(dr_parsed* parsed);
  * lit_types[k] (dr_pred_type), integer/date/boolean literals in lit_i64[k], strings as
  * lit_str_off[k]..lit_str_off[k+1] into lit_str_bytes; lit_null[k] marks a NULL literal.
  * The program must leave one boolean on the stack; rows where it is TRUE are selected.
- * Output: selected live-file ordinals (indices into the DR_LIVE export order). */
+ * Output: selected live-file ordinals (indices into the DR_LIVE export order).
+ *
+ * Literals of the other types:
+ *   DR_T_FLOAT      lit_i64[k] = the binary32 bits, zero-extended
+ *   DR_T_DOUBLE     lit_i64[k] = the binary64 bits
+ *   DR_T_TIMESTAMP  lit_i64[k] = microseconds since the epoch (UTC)
+ *   DR_T_DECIMAL | p << 8 | s << 16
+ *                   the unscaled value as 16 bytes, little-endian two's complement, at
+ *                   lit_str_bytes[lit_str_off[k] ..]; lit_i64[k] is ignored
+ *   DR_T_BINARY     the bytes in lit_str_bytes, as a string
+ * FLOAT / DOUBLE order and equality (=, !=, <=>, < .. >=, IN with In.eval's ordering.equiv) are
+ * SQLOrderingUtil.compareFloats / compareDoubles: -0.0 = 0.0, NaN = NaN, NaN above +Infinity. A
+ * TIMESTAMP compares as its microseconds, a DECIMAL as its unscaled 128-bit integer, BINARY as
+ * unsigned bytes. A column takes literals of its own type (a decimal's p and s included: widening
+ * between decimal types is the caller's), and a FLOAT column also a DOUBLE literal (the value is
+ * widened exactly, Catalyst's `floatcol > 1.5`). Anything else among these types, a decimal literal
+ * that is not 16 bytes, one with |unscaled| >= 10^p, or a non-NULL literal whose type is no
+ * dr_pred_type code, is DR_E_INVALID_ARG naming the literal index, before any device work. STRING, the integer types, DATE and BOOLEAN among themselves are not
+ * checked, as before. */
 enum dr_pred_type { DR_T_STRING = 0, DR_T_BYTE = 1, DR_T_SHORT = 2, DR_T_INT = 3, DR_T_LONG = 4,
                     DR_T_DATE = 5, DR_T_BOOLEAN = 6,
-                    /* partitionValues_parsed of the checkpoint writer only (not in predicate programs):
-                       Cast(string AS float / double / timestamp (session zone UTC) / binary /
-                       decimal(p, s)); a decimal's code carries p << 8 | s << 16 */
+                    /* Cast(string AS float / double / timestamp (session zone UTC) / binary /
+                       decimal(p, s)); a decimal's code carries p << 8 | s << 16. In
+                       partitionValues_parsed of the checkpoint writer since ABI 2, in predicate
+                       programs by the addition within ABI 4 above */
                     DR_T_FLOAT = 7, DR_T_DOUBLE = 8, DR_T_TIMESTAMP = 9, DR_T_BINARY = 10, DR_T_DECIMAL = 11 };
 enum dr_pred_opcode {
   DR_OP_COL = 0,      /* arg = column index: push Cast(partitionValues[col] AS type) */

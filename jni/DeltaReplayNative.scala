@@ -117,7 +117,11 @@ object DeltaReplayNative {
   }
 
   /** A lowered partition predicate (dr_predicate), serialised as filter() reads it. Opcodes and type
-   *  codes are include/deltareplay.h's dr_pred_opcode / dr_pred_type. */
+   *  codes are include/deltareplay.h's dr_pred_opcode / dr_pred_type. A literal is (type, isNull,
+   *  long value, bytes): integers, dates, booleans and timestamps (microseconds) in the long; a
+   *  float's binary32 bits (zero-extended) or a double's binary64 bits in the long; strings and
+   *  binaries in the bytes; a decimal (type 11 | p << 8 | s << 16, the column's own p and s) as its
+   *  unscaled value in 16 little-endian two's-complement bytes. */
   final case class Program(ops: Seq[(Int, Int)], cols: Seq[(String, Int)],
                            lits: Seq[(Int, Boolean, Long, Array[Byte])]) {
     def serialize: Array[Byte] = {
