@@ -18,13 +18,19 @@ JL_HOST := build/libjsonlane_host.so
 LIB_BOUNDS := delta_amd/libdeltareplay_bounds.so
 BOUNDS_OBJS := $(filter-out $(OBJDIR)/k_json.o,$(HIP_OBJS)) $(OBJDIR)/k_json_bounds.o
 
-all: $(LIB) $(LIB_BOUNDS) oracle $(JL_HOST)
+LK_HOST := build/liblikelane_host.so
+
+all: $(LIB) $(LIB_BOUNDS) oracle $(JL_HOST) $(LK_HOST)
 
 # host build of the K1 line walker, fuzzed against Python json by tests/test_json_lane.py
 $(JL_HOST): tests/native/json_lane_host.cpp $(CSRC)/json_lane.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -o $@ $<
 
+# host build of the K5 pattern matcher, fuzzed against Python re by tests/test_like_lane.py
+$(LK_HOST): tests/native/like_lane_host.cpp $(CSRC)/like_lane.h
+	@mkdir -p build
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -o $@ $<
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)

@@ -36,6 +36,7 @@
 #include "common.h"
 #include "json_host.h"
 #include "kernels.h"
+#include "like_lane.h"
 #include "log_segment.h"
 #include "parquet_meta.h"
 
@@ -3287,6 +3288,93 @@ static void literal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t
   else if (base == DR_T_DECIMAL) decimal_words(p, k, lo, hi);
 }
 
+// ---- string patterns (DR_OP_STARTSWITH .. DR_OP_LIKE) ------------------------------------------------
+static bool is_pattern_op(int op) { return op >= DR_OP_STARTSWITH && op <= DR_OP_LIKE; }
+static const char* pattern_op_name(int op) {
+  return op == DR_OP_STARTSWITH ? "STARTSWITH" : op == DR_OP_ENDSWITH ? "ENDSWITH" : op == DR_OP_CONTAINS ? "CONTAINS" : "LIKE";
+}
+static std::string pred_op_text(const dr_predicate& p, int32_t k) {
+  const int op = p.ops[k].opcode, arg = p.ops[k].arg;
+  if (op == DR_OP_COL) return fmt("partition column %s of type %d", p.col_names[arg], p.col_types[arg]);
+  if (op == DR_OP_LIT) return p.lit_null[arg] ? std::string("a NULL literal") : fmt("literal %d of type %d", arg, p.lit_types[arg]);
+  return fmt("the result of op %d (opcode %d)", k, op);
+}
+static lk::LikeCompiled compile_like(const dr_predicate& p, int32_t lit, int32_t escape) {
+  const int64_t b = p.lit_str_off[lit], e = p.lit_str_off[lit + 1];
+  return lk::like_compile(p.lit_str_bytes + b, size_t(e - b), uint32_t(escape));
+}
+// Pattern op k over the operands rooted at ops vk (value) and pk (pattern): the value a STRING
+// partition column, the pattern a STRING or NULL literal, a LIKE pattern well-formed.
+static void check_pattern_op(const dr_predicate& p, int32_t k, int32_t vk, int32_t pk) {
+  const int op = p.ops[k].opcode;
+  const char* name = pattern_op_name(op);
+  if (p.ops[vk].opcode != DR_OP_COL || p.col_types[p.ops[vk].arg] != DR_T_STRING)
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the value must be a STRING partition column, found %s", k, name,
+                               pred_op_text(p, vk).c_str()));
+  const int32_t l = p.ops[pk].arg;
+  if (p.ops[pk].opcode != DR_OP_LIT || (!p.lit_null[l] && p.lit_types[l] != DR_T_STRING))
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the pattern must be a STRING or NULL literal, found %s", k, name,
+                               pred_op_text(p, pk).c_str()));
+  if (!p.lit_null[l] && (!p.lit_str_off || p.lit_str_off[l] < 0 || p.lit_str_off[l + 1] < p.lit_str_off[l] ||
+                         (p.lit_str_off[l + 1] > p.lit_str_off[l] && !p.lit_str_bytes)))
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): literal %d has no valid bytes", k, name, l));
+  if (op != DR_OP_LIKE) return;
+  const int32_t esc = p.ops[k].arg;
+  if (esc < 1 || esc > 0xFFFF || (esc >= 0xD800 && esc <= 0xDFFF))
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (LIKE): the escape character (arg %d) must be a code point in 1..0xFFFF and no surrogate", k, esc));
+  if (p.lit_null[l]) return;
+  const lk::LikeCompiled c = compile_like(p, l, esc);
+  if (!c.error.empty()) fail(DR_E_INVALID_ARG, fmt("predicate op %d (LIKE): %s", k, c.error.c_str()));
+}
+
+// A checked program with its LIKE ops compiled (once per call): every non-NULL LIKE pattern is
+// replaced by a new literal -- the needle of the cheaper op its shape folds into (no wildcard: EQ,
+// `abc%`: STARTSWITH, `%abc`: ENDSWITH, `%abc%`: CONTAINS, `%`: STARTSWITH of the empty string, which
+// unlike IS NOT NULL stays NULL for a NULL value under NOT), or the byte program of like_lane.h under
+// DR_OP_LIKE. All three evaluators read these bytes. Returns false when the program has no such op.
+struct PatternPred {
+  dr_predicate p;
+  std::vector<dr_pred_op> ops;
+  std::vector<int32_t> lit_types;
+  std::vector<int64_t> lit_i64, lit_str_off;
+  std::vector<uint8_t> lit_null, bytes;
+};
+static bool compile_patterns(const dr_predicate& p, PatternPred& out) {
+  bool any = false;
+  for (int32_t k = 0; k < p.nops; ++k) any |= p.ops[k].opcode == DR_OP_LIKE && !p.lit_null[p.ops[k - 1].arg];
+  if (!any) return false;
+  const size_t nl = size_t(p.nlits);
+  out.ops.assign(p.ops, p.ops + p.nops);
+  out.lit_types.assign(p.lit_types, p.lit_types + nl);
+  out.lit_i64.assign(p.lit_i64, p.lit_i64 + nl);
+  out.lit_null.assign(p.lit_null, p.lit_null + nl);
+  out.lit_str_off.assign(p.lit_str_off, p.lit_str_off + nl + 1);
+  if (out.lit_str_off.back() > 0) out.bytes.assign(p.lit_str_bytes, p.lit_str_bytes + out.lit_str_off.back());
+  for (int32_t k = 0; k < p.nops; ++k) {
+    if (p.ops[k].opcode != DR_OP_LIKE || p.lit_null[p.ops[k - 1].arg]) continue;
+    const lk::LikeCompiled c = compile_like(p, p.ops[k - 1].arg, p.ops[k].arg);
+    out.ops[size_t(k) - 1].arg = int32_t(out.lit_types.size());
+    out.ops[size_t(k)].opcode = c.kind == lk::LIKE_EQ ? DR_OP_EQ : c.kind == lk::LIKE_STARTSWITH ? DR_OP_STARTSWITH
+                              : c.kind == lk::LIKE_ENDSWITH ? DR_OP_ENDSWITH : c.kind == lk::LIKE_CONTAINS ? DR_OP_CONTAINS
+                              : DR_OP_LIKE;
+    out.ops[size_t(k)].arg = 0;
+    out.lit_types.push_back(DR_T_STRING);
+    out.lit_i64.push_back(0);
+    out.lit_null.push_back(0);
+    out.bytes.insert(out.bytes.end(), c.text.begin(), c.text.end());
+    out.lit_str_off.push_back(int64_t(out.bytes.size()));
+  }
+  out.p = p;
+  out.p.ops = out.ops.data();
+  out.p.nlits = int32_t(out.lit_types.size());
+  out.p.lit_types = out.lit_types.data();
+  out.p.lit_i64 = out.lit_i64.data();
+  out.p.lit_null = out.lit_null.data();
+  out.p.lit_str_off = out.lit_str_off.data();
+  out.p.lit_str_bytes = out.bytes.data();
+  return true;
+}
+
 // Host validation of the postfix program: types, literals, operand indices and stack discipline.
 static void check_program(const dr_predicate& p) {
   if (p.ncols < 0 || uint32_t(p.ncols) > filter_max_cols())
@@ -3343,10 +3431,14 @@ static void check_program(const dr_predicate& p) {
       case DR_OP_ISNULL: case DR_OP_ISNOTNULL: case DR_OP_NOT:
         pops = 1;
         break;
+      case DR_OP_STARTSWITH: case DR_OP_ENDSWITH: case DR_OP_CONTAINS: case DR_OP_LIKE:
+        pops = 2;
+        break;
       default: fail(DR_E_INVALID_ARG, fmt("unknown predicate opcode %d", op));
     }
     if (stack.size() < pops)
       fail(DR_E_INVALID_ARG, op == DR_OP_IN ? "predicate stack underflow (IN)" : "predicate stack underflow");
+    if (is_pattern_op(op)) check_pattern_op(p, k, stack[stack.size() - 2], stack.back());
     // a literal compared with a column must be of a kind the column takes (lit_fits)
     auto fits = [&](int32_t ck, int32_t lk) {
       if (p.ops[ck].opcode != DR_OP_COL || p.ops[lk].opcode != DR_OP_LIT) return;
@@ -3504,6 +3596,17 @@ static bool leafify(const dr_predicate& p, LeafPlan& L) {
         if (!p.lit_null[l] && !kind_ok(c, l)) return false;
         const bool widen = !p.lit_null[l] && p.col_types[c] == DR_T_FLOAT && p.lit_types[l] == DR_T_DOUBLE;
         return push_leaf(FilterLeaf{c, fop, slot(l), 0, p.lit_null[l] ? 1 : 0, widen ? 2 : 0});
+      }
+      case DR_OP_STARTSWITH: case DR_OP_ENDSWITH: case DR_OP_CONTAINS: case DR_OP_LIKE: {
+        // check_program: a STRING column and a STRING or NULL literal (LIKE: compiled, compile_patterns)
+        const int32_t l = p.ops[ch[1]].arg;
+        if (p.lit_null[l]) {  // NULL whatever the value; its type field may hold anything
+          L.i64.push_back(0);
+          L.i64hi.push_back(0);
+          L.str.emplace_back();
+          return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, int32_t(L.i64.size() - 1), 0, 1, 0});
+        }
+        return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, slot(l), 0, 0, 0});
       }
       case DR_OP_IN: {
         if (!is_col(ch[0])) return false;
@@ -4648,9 +4751,11 @@ static void build_dict(dr_state& st, dr_state::PvCol& col) {
   col.dict = 1;
 }
 
-static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& pred) {
+static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& given) {
   DR_STAGE("filter", st.ctx->stream);
-  check_program(pred);
+  check_program(given);
+  PatternPred compiled;
+  const dr_predicate& pred = compile_patterns(given, compiled) ? compiled.p : given;
   dr_ctx* ctx = st.ctx;
   ctx->begin_call();
   ensure_ready(st);
@@ -4708,7 +4813,7 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& pred)
       for (int32_t u = 0; u < la.nucol; ++u)
         if (la.ucol[u] == f.col) f.slot = u;
       f.ctype = leaf_kind(la.cols[f.col].type);
-      la.extended |= f.ctype == DR_T_FLOAT || f.ctype == DR_T_DOUBLE || f.ctype == DR_T_DECIMAL;
+      la.extended |= f.ctype == DR_T_FLOAT || f.ctype == DR_T_DOUBLE || f.ctype == DR_T_DECIMAL || is_pattern_op(f.op);
     }
     const uint64_t ng = filter_leaf_groups(st.n_live);
     DBuf<uint64_t> mask(ctx, uint64_t(filter_leaf_mask_words()) * ng), wg_off(ctx, ng + 1);

@@ -12,6 +12,7 @@
 // (include/deltareplay.h, dr_pred_op) over the typed columns.
 #include "dev_common.h"
 #include "kernels.h"
+#include "like_lane.h"
 #include "../../include/deltareplay.h"
 #include <hipcub/device/device_merge_sort.hpp>
 
@@ -770,6 +771,20 @@ __global__ void __launch_bounds__(256) k_filter_typed(FilterTypedArgs a) {
         st[sp++] = r;
         break;
       }
+      // StartsWith / EndsWith / Contains / Like(value, pattern): NULL if either is; the host has
+      // checked both are strings and replaced a LIKE pattern by its compiled program (like_lane.h)
+      case DR_OP_STARTSWITH: case DR_OP_ENDSWITH: case DR_OP_CONTAINS: case DR_OP_LIKE: {
+        const SV y = st[--sp], x = st[--sp];
+        SV r{0, nullptr, 0, 1, 0};
+        if (!x.null && !y.null) {
+          r.null = 0;
+          r.v = op == DR_OP_STARTSWITH ? lk::starts_with(x.s, x.n, y.s, y.n)
+              : op == DR_OP_ENDSWITH ? lk::ends_with(x.s, x.n, y.s, y.n)
+              : op == DR_OP_CONTAINS ? lk::contains(x.s, x.n, y.s, y.n) : lk::like_match(x.s, x.n, y.s, y.n);
+        }
+        st[sp++] = r;
+        break;
+      }
       case DR_OP_NSEQ: {
         const SV y = st[--sp], x = st[--sp];
         SV r{0, nullptr, 0, 0, 0};
@@ -862,8 +877,9 @@ constexpr uint32_t FL_FILES = FL_T * FL_PER;  // files per tile (4 FL_PER mask w
 // The leaf result from a column value already in registers (nul, v = integer or big-endian 8-byte
 // string prefix, vn = string length); the long-string gather reads the column by file ordinal i.
 // The literals are the workgroup's LDS copies (li: integers and IN sets, ls8 / lso: the string
-// literals' prefixes and offsets). X: the leaf may be of a FLOAT / DOUBLE / DECIMAL column (the
-// kernels for the older types are instantiated without that code: k_filter_leaf is register-tuned).
+// literals' prefixes and offsets). X: the leaf may be of a FLOAT / DOUBLE / DECIMAL column or a
+// string pattern (the kernels for the older types and ops are instantiated without that code:
+// k_filter_leaf is register-tuned).
 template <bool X>
 __device__ __forceinline__ uint32_t leaf_value(const uint8_t* lit_str, const FilterLeaf& L, const PvColumn& col,
                                                uint64_t i, uint32_t nul, int64_t v, uint32_t vn, const int64_t* li,
@@ -898,6 +914,27 @@ __device__ __forceinline__ uint32_t leaf_value(const uint8_t* lit_str, const Fil
     const int64_t x = li[k];
     return v == x ? 0 : (v < x ? -1 : 1);
   };
+  if (X && L.op >= DR_OP_STARTSWITH) {  // uniform: a string pattern; literal L.lit is the needle / the LIKE program
+    const uint64_t o = lso[L.lit];
+    const uint32_t ln = uint32_t(lso[L.lit + 1] - o);
+    const uint8_t* pat = lit_str + o;
+    if (L.op == DR_OP_LIKE) return lk::like_match(reinterpret_cast<const uint8_t*>(col.sptr[i]), vn, pat, ln) ? 1u : 0u;
+    if (ln > vn) return 0u;
+    if (ln == 0) return 1u;
+    const uint64_t l8 = ls8[L.lit];
+    if (L.op == DR_OP_STARTSWITH) {  // the first 8 bytes from the register prefix, the rest gathered
+      const uint64_t m = ln >= 8 ? ~0ull : ~0ull << (64 - 8 * ln);
+      if ((v8 & m) != l8) return 0u;
+      if (ln <= 8) return 1u;
+      return lk::bytes_eq(reinterpret_cast<const uint8_t*>(col.sptr[i]) + 8, pat + 8, ln - 8) ? 1u : 0u;
+    }
+    if (L.op == DR_OP_ENDSWITH && vn <= 8) {  // both in registers, right-aligned
+      const uint64_t m = ln >= 8 ? ~0ull : (1ull << (8 * ln)) - 1;
+      return ((v8 >> (64 - 8 * vn)) & m) == (l8 >> (64 - 8 * ln)) ? 1u : 0u;
+    }
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(col.sptr[i]);
+    return (L.op == DR_OP_ENDSWITH ? lk::ends_with(s, vn, pat, ln) : lk::contains(s, vn, pat, ln)) ? 1u : 0u;
+  }
   if (L.op == DR_OP_IN && L.pad == 1) {  // an integer set as a bitmap over [min, min + 64 * words)
     const uint64_t d = uint64_t(v) - uint64_t(li[L.lit]);
     const uint64_t nbits = uint64_t(li[L.lit + 1]) * 64;
@@ -1063,7 +1100,8 @@ __device__ __forceinline__ void filter_leaf_tiles(const FilterLeafArgs& a) {
 }
 // k_filter_leaf: programs over STRING / BINARY, the integer kinds, DATE, BOOLEAN and TIMESTAMP
 // columns, exactly the code it was before the other types; k_filter_leaf_x: programs with a leaf
-// over a FLOAT, DOUBLE or DECIMAL column (FilterLeafArgs::extended, set by the host).
+// over a FLOAT, DOUBLE or DECIMAL column or a string pattern leaf (FilterLeafArgs::extended, set by
+// the host).
 __global__ void __launch_bounds__(FL_T) k_filter_leaf(FilterLeafArgs a) { filter_leaf_tiles<false>(a); }
 __global__ void __launch_bounds__(FL_T) k_filter_leaf_x(FilterLeafArgs a) { filter_leaf_tiles<true>(a); }
 

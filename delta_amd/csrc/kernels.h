@@ -509,7 +509,8 @@ struct FilterTypedArgs {
 // three-valued results on a 2-bit-per-entry stack held in one register.
 struct FilterLeaf {
   int32_t col;       // predicate column
-  int32_t op;        // DR_OP_EQ .. DR_OP_GE, DR_OP_NSEQ, DR_OP_IN, DR_OP_ISNULL, DR_OP_ISNOTNULL
+  int32_t op;        // DR_OP_EQ .. DR_OP_GE, DR_OP_NSEQ, DR_OP_IN, DR_OP_ISNULL, DR_OP_ISNOTNULL,
+                     // DR_OP_STARTSWITH .. DR_OP_LIKE (literal `lit`: the needle / like_lane.h's program)
   int32_t lit;       // literal index (comparisons) or first entry of the sorted set (IN)
   int32_t nlit;      // IN: entries in the set
   int32_t lit_null;  // comparisons: the literal is NULL; IN: the list holds a NULL
@@ -536,7 +537,7 @@ struct FilterLeafArgs {
   int32_t nucol;                 // distinct columns the leaves read (0: more than FL_UCOLS, loaded per leaf)
   int32_t ucol[4];               // FL_UCOLS: those columns (predicate column indices)
   const int64_t* lit_hi;         // [n_i64] DECIMAL literals' high words (read by decimal leaves only)
-  int32_t extended;              // a leaf reads a FLOAT / DOUBLE / DECIMAL column: k_filter_leaf_x
+  int32_t extended;              // a leaf reads a FLOAT / DOUBLE / DECIMAL column or is a string pattern: k_filter_leaf_x
 };
 constexpr int FL_UCOLS = 4;
 uint32_t filter_leaf_max_prog();

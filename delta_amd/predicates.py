@@ -11,7 +11,10 @@ Mirrors the reference's metadata-predicate handling:
 
 Expressions are nested tuples (the oracle's format): ("col", name), ("lit", type, value),
 (op, a, b) for = != < <= > >= <=>, ("in", a, [lits]), ("isnull", a), ("isnotnull", a),
-("and", a, b), ("or", a, b), ("not", a). Types: "string", "byte", "short", "integer", "long",
+("and", a, b), ("or", a, b), ("not", a), and the string patterns ("startswith", col, lit),
+("endswith", col, lit), ("contains", col, lit), ("like", col, lit[, escape]) -- Catalyst's StartsWith /
+EndsWith / Contains / Like over a string partition column and a string (or NULL) literal; the escape
+is one character, Spark's default "\\". Types: "string", "byte", "short", "integer", "long",
 "date", "boolean", "float", "double", "timestamp", "binary", "decimal(p,s)" ("decimal" is
 decimal(10,0)). The program is evaluated on the GPU; nothing here evaluates it.
 
@@ -51,7 +54,9 @@ def type_code(typ: str) -> Optional[int]:
     return None
 OP_COL, OP_LIT = 0, 1
 OP_CODE = {"=": 2, "!=": 3, "<": 4, "<=": 5, ">": 6, ">=": 7, "<=>": 8, "in": 9, "isnull": 10,
-           "isnotnull": 11, "and": 12, "or": 13, "not": 14}
+           "isnotnull": 11, "and": 12, "or": 13, "not": 14,
+           "startswith": 15, "endswith": 16, "contains": 17, "like": 18}
+PATTERN_OPS = ("startswith", "endswith", "contains", "like")
 _EPOCH = _dt.date(1970, 1, 1)
 
 
@@ -76,6 +81,8 @@ def _refs(expr) -> List[str]:
         return []
     if op == "in":
         return _refs(expr[1]) + [r for l in expr[2] for r in _refs(l)]
+    if op == "like":  # a fourth element is the escape character, no expression
+        return _refs(expr[1]) + _refs(expr[2])
     return [r for a in expr[1:] for r in _refs(a)]
 
 
@@ -416,6 +423,30 @@ def _lit(typ: str, v):
     return int(v)
 
 
+def like_escape_code(escape) -> int:
+    """The escape character of a LIKE as DR_OP_LIKE's arg: one character, a code point in 1..0xFFFF
+    and no surrogate (Like's escapeChar is a JVM Char)."""
+    if not isinstance(escape, str) or len(escape) != 1 or not 1 <= ord(escape) <= 0xFFFF or 0xD800 <= ord(escape) <= 0xDFFF:
+        raise PredicateError("like: the escape must be one character (a code point in 1..0xFFFF, no surrogate), got %r"
+                             % (escape,))
+    return ord(escape)
+
+
+def check_like_pattern(pattern: str, escape: str) -> None:
+    """StringUtils.escapeLikeRegex's two errors, with its texts (dr_filter reports the same)."""
+    i = 0
+    while i < len(pattern):
+        if pattern[i] == escape:
+            if i + 1 == len(pattern):
+                raise PredicateError("the pattern '%s' is invalid, it is not allowed to end with the escape character"
+                                     % pattern)
+            if pattern[i + 1] not in ("_", "%", escape):
+                raise PredicateError("the pattern '%s' is invalid, the escape character is not allowed to precede '%s'"
+                                     % (pattern, pattern[i + 1]))
+            i += 1
+        i += 1
+
+
 def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
     """AND of `preds` lowered to the postfix program of include/deltareplay.h (dr_pred_op)."""
     if not preds:
@@ -452,6 +483,32 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
         if (ct & 0xff >= T_FLOAT or lt & 0xff >= T_FLOAT) and not (ct == lt or (ct == T_FLOAT and lt == T_DOUBLE)):
             raise PredicateError("a %s literal does not fit partition column %s of type %s" % (b[1], exact, schema[exact]))
 
+    def pattern(e):
+        """A string pattern: the value a string partition column, the pattern a string or NULL literal."""
+        op = e[0]
+        if len(e) not in ((3, 4) if op == "like" else (3,)):
+            raise PredicateError("%s takes a column and a literal%s" % (op, " and an optional escape" if op == "like" else ""))
+        value, pat = e[1], e[2]
+        exact = _resolve(value[1], parts) if value[0] == "col" else None
+        if value[0] != "col":
+            raise PredicateError("%s: the value must be a string partition column, found %r" % (op, value[0]))
+        if exact is not None and schema[exact] != "string":
+            raise PredicateError("%s: the value must be a string partition column, %s is %s" % (op, exact, schema[exact]))
+        if pat[0] != "lit":
+            raise PredicateError("%s: the pattern must be a string or NULL literal, found %r" % (op, pat[0]))
+        if pat[2] is not None and (pat[1] != "string" or not isinstance(pat[2], str)):
+            raise PredicateError("%s: the pattern must be a string or NULL literal, found a %s literal %r"
+                                 % (op, pat[1], pat[2]))
+        arg = 0
+        if op == "like":
+            escape = e[3] if len(e) == 4 else "\\"
+            arg = like_escape_code(escape)
+            if pat[2] is not None:
+                check_like_pattern(pat[2], escape)
+        emit(value)
+        emit(pat)
+        p.ops.append((OP_CODE[op], arg))
+
     def emit(e):
         op = e[0]
         if op == "col":
@@ -467,6 +524,8 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
         elif op in ("isnull", "isnotnull", "not"):
             emit(e[1])
             p.ops.append((OP_CODE[op], 0))
+        elif op in PATTERN_OPS:
+            pattern(e)
         elif op in OP_CODE:
             if op not in ("and", "or"):
                 fits(e[1], e[2])

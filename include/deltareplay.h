@@ -425,7 +425,27 @@ int dr_parsed_release(dr_parsed* parsed);
  * widened exactly, Catalyst's `floatcol > 1.5`). Anything else among these types, a decimal literal
  * that is not 16 bytes, one with |unscaled| >= 10^p, or a non-NULL literal whose type is no
  * dr_pred_type code, is DR_E_INVALID_ARG naming the literal index, before any device work. STRING, the integer types, DATE and BOOLEAN among themselves are not
- * checked, as before. */
+ * checked, as before.
+ *
+ * String patterns (DR_OP_STARTSWITH .. DR_OP_LIKE, added within ABI 4; an older library answers
+ * "unknown predicate opcode"): each pops the pattern, then the value. The value must be a DR_OP_COL
+ * of a DR_T_STRING column and the pattern a DR_OP_LIT of type DR_T_STRING or a NULL literal; anything
+ * else (a non-string or DR_T_BINARY column, a pattern that is no literal, a literal of another type)
+ * is DR_E_INVALID_ARG naming the op index and what was found, before any device work. Catalyst casts
+ * a non-string child of Like to string first: that is out of scope here.
+ * Spark 3.1 semantics: a NULL value or a NULL pattern gives NULL (not selected, and NULL under NOT).
+ * StartsWith / EndsWith / Contains are UTF8String's bytewise prefix, suffix and substring tests; an
+ * empty pattern is TRUE for every non-NULL value. Like is StringUtils.escapeLikeRegex and a full
+ * match with (?s), the pattern read code point by code point: the escape character followed by `_`,
+ * `%` or itself is that character literally (the escape test comes first: with escape `%` the pattern
+ * `%%` is a literal `%`); `_` is exactly one code point, newline included; `%` is any run, the empty
+ * one included; every other character is itself. DR_E_INVALID_ARG with Spark's texts for the escape
+ * character before anything else ("the escape character is not allowed to precede '...'") or as the
+ * last character ("it is not allowed to end with the escape character"), and for an escape outside
+ * 1..0xFFFF, a surrogate escape, or a pattern that is not valid UTF-8.
+ * A partition value that is not valid UTF-8 (Java decodes it with replacement characters first:
+ * parity unpinned) is read as characters of one non-continuation byte plus the continuation bytes
+ * after it, continuation bytes before the first other byte being one character each. */
 enum dr_pred_type { DR_T_STRING = 0, DR_T_BYTE = 1, DR_T_SHORT = 2, DR_T_INT = 3, DR_T_LONG = 4,
                     DR_T_DATE = 5, DR_T_BOOLEAN = 6,
                     /* Cast(string AS float / double / timestamp (session zone UTC) / binary /
@@ -440,7 +460,9 @@ enum dr_pred_opcode {
   DR_OP_NSEQ = 8,     /* <=> */
   DR_OP_IN = 9,       /* arg = number of literals pushed after the value */
   DR_OP_ISNULL = 10, DR_OP_ISNOTNULL = 11,
-  DR_OP_AND = 12, DR_OP_OR = 13, DR_OP_NOT = 14
+  DR_OP_AND = 12, DR_OP_OR = 13, DR_OP_NOT = 14,
+  DR_OP_STARTSWITH = 15, DR_OP_ENDSWITH = 16, DR_OP_CONTAINS = 17,  /* arg unused (0) */
+  DR_OP_LIKE = 18     /* arg = the escape character as a code point (Spark's default '\\' = 92) */
 };
 typedef struct dr_pred_op { int32_t opcode; int32_t arg; } dr_pred_op;
 

@@ -121,7 +121,10 @@ object DeltaReplayNative {
    *  long value, bytes): integers, dates, booleans and timestamps (microseconds) in the long; a
    *  float's binary32 bits (zero-extended) or a double's binary64 bits in the long; strings and
    *  binaries in the bytes; a decimal (type 11 | p << 8 | s << 16, the column's own p and s) as its
-   *  unscaled value in 16 little-endian two's-complement bytes. */
+   *  unscaled value in 16 little-endian two's-complement bytes.
+   *  String patterns over a STRING column and a STRING (or NULL) literal, value first, pattern second:
+   *  DR_OP_STARTSWITH = 15, DR_OP_ENDSWITH = 16, DR_OP_CONTAINS = 17 (arg 0) and DR_OP_LIKE = 18, whose
+   *  arg is Like.escapeChar as a code point ('\\' = 92). */
   final case class Program(ops: Seq[(Int, Int)], cols: Seq[(String, Int)],
                            lits: Seq[(Int, Boolean, Long, Array[Byte])]) {
     def serialize: Array[Byte] = {
