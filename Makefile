@@ -4,7 +4,7 @@ ARCH ?= gfx950
 CSRC := delta_amd/csrc
 LIB := delta_amd/libdeltareplay.so
 HIP_SRCS := $(CSRC)/engine.hip $(CSRC)/k_json.hip $(CSRC)/k_parquet.hip $(CSRC)/k_snappy.hip $(CSRC)/k_replay.hip $(CSRC)/k_util.hip $(CSRC)/k_shard.hip $(CSRC)/k_filter.hip $(CSRC)/k_index.hip $(CSRC)/k_encode.hip $(CSRC)/k_rows.hip $(CSRC)/k_lookup.hip
-CXX_SRCS := $(CSRC)/parquet_meta.cpp $(CSRC)/log_segment.cpp $(CSRC)/json_host.cpp $(CSRC)/snappy_host.cpp
+CXX_SRCS := $(CSRC)/parquet_meta.cpp $(CSRC)/log_segment.cpp $(CSRC)/json_host.cpp $(CSRC)/snappy_host.cpp $(CSRC)/pred_plan.cpp
 OBJDIR := build/obj
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
 CXX_OBJS := $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(CXX_SRCS))
@@ -19,8 +19,9 @@ LIB_BOUNDS := delta_amd/libdeltareplay_bounds.so
 BOUNDS_OBJS := $(filter-out $(OBJDIR)/k_json.o,$(HIP_OBJS)) $(OBJDIR)/k_json_bounds.o
 
 LK_HOST := build/liblikelane_host.so
+PP_HOST := build/libpredplan_host.so
 
-all: $(LIB) $(LIB_BOUNDS) oracle $(JL_HOST) $(LK_HOST)
+all: $(LIB) $(LIB_BOUNDS) oracle $(JL_HOST) $(LK_HOST) $(PP_HOST)
 
 # host build of the K1 line walker, fuzzed against Python json by tests/test_json_lane.py
 $(JL_HOST): tests/native/json_lane_host.cpp $(CSRC)/json_lane.h
@@ -31,6 +32,11 @@ $(JL_HOST): tests/native/json_lane_host.cpp $(CSRC)/json_lane.h
 $(LK_HOST): tests/native/like_lane_host.cpp $(CSRC)/like_lane.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -o $@ $<
+
+# host build of the K5 predicate planner, called with real dr_predicates by tests/test_pred_plan.py
+$(PP_HOST): tests/native/pred_plan_host.cpp $(CSRC)/pred_plan.cpp $(HDRS)
+	@mkdir -p build
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -o $@ tests/native/pred_plan_host.cpp $(CSRC)/pred_plan.cpp
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)

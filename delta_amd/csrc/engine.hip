@@ -39,6 +39,7 @@
 #include "like_lane.h"
 #include "log_segment.h"
 #include "parquet_meta.h"
+#include "pred_plan.h"
 
 // ---- stage ranges (SURVEY.md §5 tracing) --------------------------------------------------------------
 // roctx ranges around the replay's stages -- parse.json, decode.checkpoint, canonicalize,
@@ -3254,437 +3255,12 @@ static void build_export(dr_state& st, int which) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K5: partition pruning (DeltaLog.filterFileList, D/DeltaLog.scala:500-547)
+// K5: partition pruning (DeltaLog.filterFileList, D/DeltaLog.scala:500-547): the typed cache columns,
+// their dictionaries and the filter call. The predicate planner it calls is pred_plan.cpp.
 // ---------------------------------------------------------------------------------------------------
 static const char* kPvKey = "add.partitionValues.key_value.key";
 static const char* kPvVal = "add.partitionValues.key_value.value";
 
-// The types this PR's callers may compare: a column takes literals of its own type (a decimal's
-// precision and scale included), and a FLOAT column also a DOUBLE literal (the value is widened).
-// STRING, the integer kinds, DATE and BOOLEAN among themselves keep their old leniency (unchecked).
-static bool new_pred_type(int32_t t) { return (t & 0xff) >= DR_T_FLOAT; }
-static bool lit_fits(int32_t ctype, int32_t ltype) {
-  if (!new_pred_type(ctype) && !new_pred_type(ltype)) return true;
-  return ctype == ltype || (ctype == DR_T_FLOAT && ltype == DR_T_DOUBLE);
-}
-
-// A DECIMAL literal: 16 bytes, little-endian two's complement, in the string bytes.
-static void decimal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t* hi) {
-  uint64_t w[2];
-  std::memcpy(w, p.lit_str_bytes + p.lit_str_off[k], 16);
-  *lo = int64_t(w[0]);
-  *hi = int64_t(w[1]);
-}
-
-// Literal k as the evaluators compare it: FLOAT / DOUBLE as their order keys (fp_key32 / fp_key64,
-// the device's own functions), a DECIMAL's two words, everything else as given.
-static void literal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t* hi) {
-  *lo = p.lit_i64[k];
-  *hi = 0;
-  if (p.lit_null[k]) return;
-  const int base = p.lit_types[k] & 0xff;
-  if (base == DR_T_FLOAT) *lo = fp_key32(uint32_t(p.lit_i64[k]));
-  else if (base == DR_T_DOUBLE) *lo = fp_key64(uint64_t(p.lit_i64[k]));
-  else if (base == DR_T_DECIMAL) decimal_words(p, k, lo, hi);
-}
-
-// ---- string patterns (DR_OP_STARTSWITH .. DR_OP_LIKE) ------------------------------------------------
-static bool is_pattern_op(int op) { return op >= DR_OP_STARTSWITH && op <= DR_OP_LIKE; }
-static const char* pattern_op_name(int op) {
-  return op == DR_OP_STARTSWITH ? "STARTSWITH" : op == DR_OP_ENDSWITH ? "ENDSWITH" : op == DR_OP_CONTAINS ? "CONTAINS" : "LIKE";
-}
-static std::string pred_op_text(const dr_predicate& p, int32_t k) {
-  const int op = p.ops[k].opcode, arg = p.ops[k].arg;
-  if (op == DR_OP_COL) return fmt("partition column %s of type %d", p.col_names[arg], p.col_types[arg]);
-  if (op == DR_OP_LIT) return p.lit_null[arg] ? std::string("a NULL literal") : fmt("literal %d of type %d", arg, p.lit_types[arg]);
-  return fmt("the result of op %d (opcode %d)", k, op);
-}
-static lk::LikeCompiled compile_like(const dr_predicate& p, int32_t lit, int32_t escape) {
-  const int64_t b = p.lit_str_off[lit], e = p.lit_str_off[lit + 1];
-  return lk::like_compile(p.lit_str_bytes + b, size_t(e - b), uint32_t(escape));
-}
-// Pattern op k over the operands rooted at ops vk (value) and pk (pattern): the value a STRING
-// partition column, the pattern a STRING or NULL literal, a LIKE pattern well-formed.
-static void check_pattern_op(const dr_predicate& p, int32_t k, int32_t vk, int32_t pk) {
-  const int op = p.ops[k].opcode;
-  const char* name = pattern_op_name(op);
-  if (p.ops[vk].opcode != DR_OP_COL || p.col_types[p.ops[vk].arg] != DR_T_STRING)
-    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the value must be a STRING partition column, found %s", k, name,
-                               pred_op_text(p, vk).c_str()));
-  const int32_t l = p.ops[pk].arg;
-  if (p.ops[pk].opcode != DR_OP_LIT || (!p.lit_null[l] && p.lit_types[l] != DR_T_STRING))
-    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the pattern must be a STRING or NULL literal, found %s", k, name,
-                               pred_op_text(p, pk).c_str()));
-  if (!p.lit_null[l] && (!p.lit_str_off || p.lit_str_off[l] < 0 || p.lit_str_off[l + 1] < p.lit_str_off[l] ||
-                         (p.lit_str_off[l + 1] > p.lit_str_off[l] && !p.lit_str_bytes)))
-    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): literal %d has no valid bytes", k, name, l));
-  if (op != DR_OP_LIKE) return;
-  const int32_t esc = p.ops[k].arg;
-  if (esc < 1 || esc > 0xFFFF || (esc >= 0xD800 && esc <= 0xDFFF))
-    fail(DR_E_INVALID_ARG, fmt("predicate op %d (LIKE): the escape character (arg %d) must be a code point in 1..0xFFFF and no surrogate", k, esc));
-  if (p.lit_null[l]) return;
-  const lk::LikeCompiled c = compile_like(p, l, esc);
-  if (!c.error.empty()) fail(DR_E_INVALID_ARG, fmt("predicate op %d (LIKE): %s", k, c.error.c_str()));
-}
-
-// A checked program with its LIKE ops compiled (once per call): every non-NULL LIKE pattern is
-// replaced by a new literal -- the needle of the cheaper op its shape folds into (no wildcard: EQ,
-// `abc%`: STARTSWITH, `%abc`: ENDSWITH, `%abc%`: CONTAINS, `%`: STARTSWITH of the empty string, which
-// unlike IS NOT NULL stays NULL for a NULL value under NOT), or the byte program of like_lane.h under
-// DR_OP_LIKE. All three evaluators read these bytes. Returns false when the program has no such op.
-struct PatternPred {
-  dr_predicate p;
-  std::vector<dr_pred_op> ops;
-  std::vector<int32_t> lit_types;
-  std::vector<int64_t> lit_i64, lit_str_off;
-  std::vector<uint8_t> lit_null, bytes;
-};
-static bool compile_patterns(const dr_predicate& p, PatternPred& out) {
-  bool any = false;
-  for (int32_t k = 0; k < p.nops; ++k) any |= p.ops[k].opcode == DR_OP_LIKE && !p.lit_null[p.ops[k - 1].arg];
-  if (!any) return false;
-  const size_t nl = size_t(p.nlits);
-  out.ops.assign(p.ops, p.ops + p.nops);
-  out.lit_types.assign(p.lit_types, p.lit_types + nl);
-  out.lit_i64.assign(p.lit_i64, p.lit_i64 + nl);
-  out.lit_null.assign(p.lit_null, p.lit_null + nl);
-  out.lit_str_off.assign(p.lit_str_off, p.lit_str_off + nl + 1);
-  if (out.lit_str_off.back() > 0) out.bytes.assign(p.lit_str_bytes, p.lit_str_bytes + out.lit_str_off.back());
-  for (int32_t k = 0; k < p.nops; ++k) {
-    if (p.ops[k].opcode != DR_OP_LIKE || p.lit_null[p.ops[k - 1].arg]) continue;
-    const lk::LikeCompiled c = compile_like(p, p.ops[k - 1].arg, p.ops[k].arg);
-    out.ops[size_t(k) - 1].arg = int32_t(out.lit_types.size());
-    out.ops[size_t(k)].opcode = c.kind == lk::LIKE_EQ ? DR_OP_EQ : c.kind == lk::LIKE_STARTSWITH ? DR_OP_STARTSWITH
-                              : c.kind == lk::LIKE_ENDSWITH ? DR_OP_ENDSWITH : c.kind == lk::LIKE_CONTAINS ? DR_OP_CONTAINS
-                              : DR_OP_LIKE;
-    out.ops[size_t(k)].arg = 0;
-    out.lit_types.push_back(DR_T_STRING);
-    out.lit_i64.push_back(0);
-    out.lit_null.push_back(0);
-    out.bytes.insert(out.bytes.end(), c.text.begin(), c.text.end());
-    out.lit_str_off.push_back(int64_t(out.bytes.size()));
-  }
-  out.p = p;
-  out.p.ops = out.ops.data();
-  out.p.nlits = int32_t(out.lit_types.size());
-  out.p.lit_types = out.lit_types.data();
-  out.p.lit_i64 = out.lit_i64.data();
-  out.p.lit_null = out.lit_null.data();
-  out.p.lit_str_off = out.lit_str_off.data();
-  out.p.lit_str_bytes = out.bytes.data();
-  return true;
-}
-
-// Host validation of the postfix program: types, literals, operand indices and stack discipline.
-static void check_program(const dr_predicate& p) {
-  if (p.ncols < 0 || uint32_t(p.ncols) > filter_max_cols())
-    fail(DR_E_UNSUPPORTED, fmt("at most %u partition columns per predicate", filter_max_cols()));
-  if (p.nops <= 0 || !p.ops) fail(DR_E_INVALID_ARG, "empty predicate program");
-  if (p.ncols && (!p.col_names || !p.col_types)) fail(DR_E_INVALID_ARG, "missing partition columns");
-  if (p.nlits && (!p.lit_types || !p.lit_i64 || !p.lit_null || !p.lit_str_off))
-    fail(DR_E_INVALID_ARG, "missing literals");
-  // a type code: STRING .. BINARY bare, DECIMAL | p << 8 | s << 16 with 1 <= p <= 38, s <= p
-  auto type_ok = [](int32_t t) {
-    if (t < 0) return false;
-    if ((t & 0xff) != DR_T_DECIMAL) return t <= DR_T_BINARY;
-    const int32_t prec = (t >> 8) & 0xff, scale = t >> 16;
-    return prec >= 1 && prec <= 38 && scale <= prec;
-  };
-  for (int32_t c = 0; c < p.ncols; ++c)
-    if (!type_ok(p.col_types[c]) || !p.col_names[c])
-      fail(DR_E_UNSUPPORTED, "unsupported partition column type");
-  for (int32_t k = 0; k < p.nlits; ++k) {
-    if (p.lit_null[k]) continue;
-    const int32_t t = p.lit_types[k];
-    if (!type_ok(t)) fail(DR_E_INVALID_ARG, fmt("predicate literal %d has no valid type (code %d)", k, t));
-    if ((t & 0xff) != DR_T_DECIMAL) continue;
-    if (!p.lit_str_bytes || p.lit_str_off[k] < 0 || p.lit_str_off[k + 1] - p.lit_str_off[k] != 16)
-      fail(DR_E_INVALID_ARG, fmt("decimal literal %d must be 16 bytes (little-endian two's complement)", k));
-    int64_t lo, hi;
-    decimal_words(p, k, &lo, &hi);
-    const __int128 v = (__int128(hi) << 64) | __int128(uint64_t(lo));
-    unsigned __int128 lim = 1;
-    for (int32_t d = 0; d < ((t >> 8) & 0xff); ++d) lim *= 10;
-    if ((v < 0 ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v) >= lim)
-      fail(DR_E_INVALID_ARG, fmt("decimal literal %d does not fit precision %d", k, (t >> 8) & 0xff));
-  }
-  // stack discipline: every op's operands are whole subtrees (postfix -> tree)
-  std::vector<int32_t> stack;
-  for (int32_t k = 0; k < p.nops; ++k) {
-    const int op = p.ops[k].opcode, arg = p.ops[k].arg;
-    size_t pops = 0;
-    switch (op) {
-      case DR_OP_COL:
-        if (arg < 0 || arg >= p.ncols) fail(DR_E_INVALID_ARG, "predicate column index out of range");
-        break;
-      case DR_OP_LIT:
-        if (arg < 0 || arg >= p.nlits) fail(DR_E_INVALID_ARG, "predicate literal index out of range");
-        break;
-      case DR_OP_EQ: case DR_OP_NE: case DR_OP_LT: case DR_OP_LE: case DR_OP_GT: case DR_OP_GE:
-      case DR_OP_NSEQ: case DR_OP_AND: case DR_OP_OR:
-        pops = 2;
-        break;
-      case DR_OP_IN:
-        if (arg < 0) fail(DR_E_INVALID_ARG, "predicate stack underflow (IN)");
-        pops = size_t(arg) + 1;
-        break;
-      case DR_OP_ISNULL: case DR_OP_ISNOTNULL: case DR_OP_NOT:
-        pops = 1;
-        break;
-      case DR_OP_STARTSWITH: case DR_OP_ENDSWITH: case DR_OP_CONTAINS: case DR_OP_LIKE:
-        pops = 2;
-        break;
-      default: fail(DR_E_INVALID_ARG, fmt("unknown predicate opcode %d", op));
-    }
-    if (stack.size() < pops)
-      fail(DR_E_INVALID_ARG, op == DR_OP_IN ? "predicate stack underflow (IN)" : "predicate stack underflow");
-    if (is_pattern_op(op)) check_pattern_op(p, k, stack[stack.size() - 2], stack.back());
-    // a literal compared with a column must be of a kind the column takes (lit_fits)
-    auto fits = [&](int32_t ck, int32_t lk) {
-      if (p.ops[ck].opcode != DR_OP_COL || p.ops[lk].opcode != DR_OP_LIT) return;
-      const int32_t c = p.ops[ck].arg, l = p.ops[lk].arg;
-      if (!p.lit_null[l] && !lit_fits(p.col_types[c], p.lit_types[l]))
-        fail(DR_E_INVALID_ARG, fmt("predicate literal %d (type %d) does not fit partition column %s (type %d)", l,
-                                   p.lit_types[l], p.col_names[c], p.col_types[c]));
-    };
-    if (op >= DR_OP_EQ && op <= DR_OP_NSEQ) {
-      const int32_t x = stack[stack.size() - 2], y = stack.back();
-      fits(x, y);
-      fits(y, x);
-    } else if (op == DR_OP_IN) {
-      for (size_t q = 1; q < pops; ++q) fits(stack[stack.size() - pops], stack[stack.size() - pops + q]);
-    }
-    stack.resize(stack.size() - pops);
-    stack.push_back(k);
-  }
-  if (stack.size() != 1) fail(DR_E_INVALID_ARG, "predicate program must leave one value");
-}
-
-// Lowers the ABI program to the device form. `x e1..en IN(n)` becomes
-// `x IN_START e1 IN_STEP .. en IN_STEP IN_END`, so an IN list of any length needs two stack slots
-// beyond its value (In.eval semantics are unchanged: true if any element equals, else null if the
-// value or any element is null, else false). Returns (opcode, arg) pairs; fails if the lowered
-// program still needs more than the device stack.
-static std::vector<int32_t> lower_program(const dr_predicate& p) {
-  // subtree extents: start[k] = first op of the subtree rooted at op k
-  std::vector<int32_t> start(size_t(p.nops)), stack;
-  std::vector<std::vector<int32_t>> kids(size_t(p.nops));
-  for (int32_t k = 0; k < p.nops; ++k) {
-    const int op = p.ops[k].opcode;
-    size_t pops = op == DR_OP_COL || op == DR_OP_LIT ? 0
-                : op == DR_OP_IN ? size_t(p.ops[k].arg) + 1
-                : (op == DR_OP_ISNULL || op == DR_OP_ISNOTNULL || op == DR_OP_NOT) ? 1 : 2;
-    kids[size_t(k)].assign(stack.end() - ptrdiff_t(pops), stack.end());
-    stack.resize(stack.size() - pops);
-    start[size_t(k)] = kids[size_t(k)].empty() ? k : start[size_t(kids[size_t(k)][0])];
-    stack.push_back(k);
-  }
-  std::vector<int32_t> out;
-  int depth = 0, max_depth = 0;
-  auto put = [&](int32_t op, int32_t arg, int delta) {
-    out.push_back(op);
-    out.push_back(arg);
-    depth += delta;
-    max_depth = std::max(max_depth, depth);
-  };
-  std::function<void(int32_t)> emit = [&](int32_t k) {
-    const int op = p.ops[k].opcode, arg = p.ops[k].arg;
-    const auto& ch = kids[size_t(k)];
-    if (op == DR_OP_IN) {
-      emit(ch[0]);
-      put(FILTER_OP_IN_START, 0, +1);
-      for (size_t q = 1; q < ch.size(); ++q) {
-        emit(ch[q]);
-        put(FILTER_OP_IN_STEP, 0, -1);
-      }
-      put(FILTER_OP_IN_END, 0, -1);
-      return;
-    }
-    for (int32_t c : ch) emit(c);
-    put(op, arg, 1 - int(ch.size()));
-  };
-  emit(p.nops - 1);
-  if (uint32_t(max_depth) > filter_max_stack()) fail(DR_E_UNSUPPORTED, "predicate program too deep");
-  return out;
-}
-
-// Leaf form of a program (k_filter_leaf) when every comparison is between one partition column and
-// literals of its kind and the rest is AND / OR / NOT: each leaf is evaluated straight from the typed
-// K5 cache, IN lists become sorted sets searched by bisection, and the boolean combination runs on
-// a register stack. Returns false (generic interpreter, k_filter_typed) for anything else.
-struct LeafPlan {
-  std::vector<FilterLeaf> leaves;
-  std::vector<int32_t> prog;
-  std::vector<int64_t> i64;        // literal slots (FLOAT / DOUBLE: order keys; DECIMAL: the low word)
-  std::vector<int64_t> i64hi;      // parallel: a DECIMAL's high word
-  std::vector<std::string> str;
-};
-static bool leafify(const dr_predicate& p, LeafPlan& L) {
-  std::vector<std::vector<int32_t>> kids(size_t(p.nops));
-  std::vector<int32_t> stack;
-  for (int32_t k = 0; k < p.nops; ++k) {
-    const int op = p.ops[k].opcode;
-    const size_t pops = op == DR_OP_COL || op == DR_OP_LIT ? 0
-                      : op == DR_OP_IN ? size_t(p.ops[k].arg) + 1
-                      : (op == DR_OP_ISNULL || op == DR_OP_ISNOTNULL || op == DR_OP_NOT) ? 1 : 2;
-    kids[size_t(k)].assign(stack.end() - ptrdiff_t(pops), stack.end());
-    stack.resize(stack.size() - pops);
-    stack.push_back(k);
-  }
-  auto is_col = [&](int32_t k) { return p.ops[k].opcode == DR_OP_COL; };
-  auto is_lit = [&](int32_t k) { return p.ops[k].opcode == DR_OP_LIT; };
-  auto is_str = [](int32_t t) { return leaf_kind(t) == DR_T_STRING; };
-  // string (and binary) columns with literals of bytes, others numeric; the new types by lit_fits
-  auto kind_ok = [&](int32_t col, int32_t lit) {
-    return is_str(p.col_types[col]) == is_str(p.lit_types[lit]) && lit_fits(p.col_types[col], p.lit_types[lit]);
-  };
-  // a FLOAT column's literal as the leaf compares it: a DOUBLE literal's key as it is (the leaf widens
-  // the value, pad = 2), and then a FLOAT literal's key widened like the value
-  auto fp_word = [&](int32_t lit, bool widen) {
-    int64_t lo, hi;
-    literal_words(p, lit, &lo, &hi);
-    return widen && p.lit_types[lit] == DR_T_FLOAT ? fp_key_widen(lo) : lo;
-  };
-  auto slot = [&](int32_t lit) {
-    int64_t lo, hi;
-    literal_words(p, lit, &lo, &hi);
-    L.i64.push_back(lo);
-    L.i64hi.push_back(hi);
-    if (is_str(p.lit_types[lit]))
-      L.str.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[lit],
-                         size_t(p.lit_str_off[lit + 1] - p.lit_str_off[lit]));
-    else L.str.emplace_back();
-    return int32_t(L.i64.size() - 1);
-  };
-  int depth = 0, max_depth = 0;
-  std::function<bool(int32_t)> emit = [&](int32_t k) -> bool {
-    const int op = p.ops[k].opcode;
-    const auto& ch = kids[size_t(k)];
-    auto push_leaf = [&](const FilterLeaf& f) {
-      L.prog.push_back(LEAF_OP_LEAF);
-      L.prog.push_back(int32_t(L.leaves.size()));
-      L.leaves.push_back(f);
-      max_depth = std::max(max_depth, ++depth);
-      return true;
-    };
-    switch (op) {
-      case DR_OP_AND: case DR_OP_OR:
-        if (!emit(ch[0]) || !emit(ch[1])) return false;
-        L.prog.push_back(op == DR_OP_AND ? LEAF_OP_AND : LEAF_OP_OR);
-        L.prog.push_back(0);
-        --depth;
-        return true;
-      case DR_OP_NOT:
-        if (!emit(ch[0])) return false;
-        L.prog.push_back(LEAF_OP_NOT);
-        L.prog.push_back(0);
-        return true;
-      case DR_OP_ISNULL: case DR_OP_ISNOTNULL:
-        if (!is_col(ch[0])) return false;
-        return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, 0, 0, 0, 0});
-      case DR_OP_EQ: case DR_OP_NE: case DR_OP_LT: case DR_OP_LE: case DR_OP_GT: case DR_OP_GE: case DR_OP_NSEQ: {
-        int32_t c, l, fop = op;
-        if (is_col(ch[0]) && is_lit(ch[1])) {
-          c = p.ops[ch[0]].arg; l = p.ops[ch[1]].arg;
-        } else if (is_lit(ch[0]) && is_col(ch[1])) {
-          c = p.ops[ch[1]].arg; l = p.ops[ch[0]].arg;
-          fop = op == DR_OP_LT ? DR_OP_GT : op == DR_OP_GT ? DR_OP_LT : op == DR_OP_LE ? DR_OP_GE
-              : op == DR_OP_GE ? DR_OP_LE : op;
-        } else {
-          return false;
-        }
-        if (!p.lit_null[l] && !kind_ok(c, l)) return false;
-        const bool widen = !p.lit_null[l] && p.col_types[c] == DR_T_FLOAT && p.lit_types[l] == DR_T_DOUBLE;
-        return push_leaf(FilterLeaf{c, fop, slot(l), 0, p.lit_null[l] ? 1 : 0, widen ? 2 : 0});
-      }
-      case DR_OP_STARTSWITH: case DR_OP_ENDSWITH: case DR_OP_CONTAINS: case DR_OP_LIKE: {
-        // check_program: a STRING column and a STRING or NULL literal (LIKE: compiled, compile_patterns)
-        const int32_t l = p.ops[ch[1]].arg;
-        if (p.lit_null[l]) {  // NULL whatever the value; its type field may hold anything
-          L.i64.push_back(0);
-          L.i64hi.push_back(0);
-          L.str.emplace_back();
-          return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, int32_t(L.i64.size() - 1), 0, 1, 0});
-        }
-        return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, slot(l), 0, 0, 0});
-      }
-      case DR_OP_IN: {
-        if (!is_col(ch[0])) return false;
-        const int32_t c = p.ops[ch[0]].arg;
-        const int kind = leaf_kind(p.col_types[c]);
-        const bool str = kind == DR_T_STRING;
-        bool has_null = false, widen = false;
-        std::vector<int64_t> iv;
-        std::vector<std::pair<int64_t, uint64_t>> dv;  // decimals: (high signed, low unsigned)
-        std::vector<std::string> sv;
-        for (size_t q = 1; q < ch.size(); ++q)  // a FLOAT column with a DOUBLE element: all in binary64
-          widen |= is_lit(ch[q]) && !p.lit_null[p.ops[ch[q]].arg] && p.col_types[c] == DR_T_FLOAT &&
-                   p.lit_types[p.ops[ch[q]].arg] == DR_T_DOUBLE;
-        for (size_t q = 1; q < ch.size(); ++q) {
-          if (!is_lit(ch[q])) return false;
-          const int32_t l = p.ops[ch[q]].arg;
-          if (p.lit_null[l]) { has_null = true; continue; }
-          if (!kind_ok(c, l)) return false;
-          if (str) {
-            sv.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[l],
-                            size_t(p.lit_str_off[l + 1] - p.lit_str_off[l]));
-          } else if (kind == DR_T_DECIMAL) {
-            int64_t lo, hi;
-            literal_words(p, l, &lo, &hi);
-            dv.emplace_back(hi, uint64_t(lo));
-          } else {
-            iv.push_back(fp_word(l, widen));  // FLOAT / DOUBLE: the key, so the set is sorted by key
-          }
-        }
-        if (kind == DR_T_DECIMAL) {  // sorted as 128-bit values
-          std::sort(dv.begin(), dv.end());
-          dv.erase(std::unique(dv.begin(), dv.end()), dv.end());
-          const int32_t first = int32_t(L.i64.size());
-          for (const auto& d : dv) {
-            L.i64.push_back(int64_t(d.second));
-            L.i64hi.push_back(d.first);
-            L.str.emplace_back();
-          }
-          return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(dv.size()), has_null ? 1 : 0, 0});
-        }
-        std::sort(iv.begin(), iv.end());
-        iv.erase(std::unique(iv.begin(), iv.end()), iv.end());
-        std::sort(sv.begin(), sv.end());  // bytewise (std::string compares as unsigned char)
-        sv.erase(std::unique(sv.begin(), sv.end()), sv.end());
-        const int32_t first = int32_t(L.i64.size());
-        const size_t m = str ? sv.size() : iv.size();
-        // an integer set spanning < 2^16 values: a bitmap, one word read per file instead of a
-        // binary search (pad = 1; literals [min, words, bits...])
-        const bool fp = kind == DR_T_FLOAT || kind == DR_T_DOUBLE;  // the bitmap: one-word integer kinds only
-        if (!str && !fp && m >= 8 && uint64_t(iv.back()) - uint64_t(iv.front()) < 65536) {
-          const uint64_t span = uint64_t(iv.back()) - uint64_t(iv.front()) + 1, nw = (span + 63) / 64;
-          std::vector<uint64_t> bits(nw, 0);
-          for (int64_t x : iv) {
-            const uint64_t d = uint64_t(x) - uint64_t(iv.front());
-            bits[d >> 6] |= uint64_t(1) << (d & 63);
-          }
-          L.i64.push_back(iv.front());
-          L.i64.push_back(int64_t(nw));
-          for (uint64_t w : bits) L.i64.push_back(int64_t(w));
-          L.i64hi.resize(L.i64.size(), 0);
-          L.str.resize(L.i64.size());
-          return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, 1});
-        }
-        for (size_t q = 0; q < m; ++q) {
-          L.i64.push_back(str ? 0 : iv[q]);
-          L.i64hi.push_back(0);
-          L.str.push_back(str ? sv[q] : std::string());
-        }
-        return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, widen ? 2 : 0});
-      }
-      default:
-        return false;
-    }
-  };
-  return emit(p.nops - 1) && max_depth <= 32;
-}
-
-// Builds the K5 cache columns `want` (name, type) of st's live AddFiles in one k_pv_extract pass.
 // Java's Double.parseDouble / Float.parseFloat for the values k_pv_extract left to the host (more
 // than 19 significant digits, exponents off Clinger's fast path, hexadecimal significands): the text
 // was already checked against the decimal grammar on the device; glibc's strtod / strtof round
@@ -3734,6 +3310,7 @@ static void fix_fp_values(dr_ctx* ctx, dr_state::PvCol& col, const DBuf<uint64_t
   HIP_OK(hipStreamSynchronize(stream));
 }
 
+// Builds the K5 cache columns `want` (name, type) of st's live AddFiles in one k_pv_extract pass.
 static void build_pv_columns(dr_state& st, const std::vector<std::pair<std::string, int32_t>>& want) {
   dr_ctx* ctx = st.ctx;
   hipStream_t stream = ctx->stream;
@@ -3886,6 +3463,254 @@ static void build_pv_columns(dr_state& st, const std::vector<std::pair<std::stri
   for (size_t c = 0; c < nc; ++c)
     if (cnt[2 + c]) fix_fp_values(ctx, *made[c], hard[c], cnt[2 + c]);
   for (auto& c : made) st.pv_cols.push_back(std::move(c));
+}
+
+static PvColumn pv_column(const dr_state::PvCol& c) {
+  PvColumn p{};
+  p.type = c.type;
+  p.w32 = c.w32.p;
+  p.w64 = c.w64.p;
+  p.sptr = c.sptr.p;
+  p.slen = c.slen.p;
+  p.isnull = c.isnull.p;
+  p.s8 = c.s8.p;
+  p.w64hi = c.w64hi.p;
+  return p;
+}
+
+// Dictionary-encodes a typed partition column (k_dict_*): abandoned (dict = 0) past DICT_MAX - 1
+// distinct values, for a DECIMAL of precision > 18 (two-word values: the key is the low word) and
+// on a string hash collision.
+static void build_dict(dr_state& st, dr_state::PvCol& col) {
+  if (col.dict >= 0) return;
+  col.dict = 0;
+  const int base = col.type & 0xff;
+  if ((base == DR_T_DECIMAL && ((col.type >> 8) & 0xff) > 18) || !st.n_live) return;
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  const uint64_t n = st.n_live;
+  DBuf<uint64_t> keys(ctx, DICT_SLOTS), scan(ctx, DICT_SLOTS + 1);
+  DBuf<uint32_t> tags(ctx, DICT_SLOTS), slot_code(ctx, DICT_SLOTS), occ(ctx, DICT_SLOTS);
+  DBuf<unsigned long long> ctr(ctx, 2);
+  DBuf<uint8_t> scratch(ctx, scan_scratch_for(DICT_SLOTS));
+  tags.zero(stream);
+  ctr.zero(stream);
+  PvDictArgs a{};
+  a.n = n;
+  a.col = pv_column(col);
+  a.key_tab = keys.p;
+  a.tag_tab = tags.p;
+  a.slot_code = slot_code.p;
+  a.ctr = ctr.p;
+  launch_dict_insert(a, stream);
+  launch_dict_occupied(a, occ.p, stream);
+  launch_scan_u32(occ.p, scan.p, DICT_SLOTS, ss(scratch), stream);
+  const uint64_t distinct = d2h_one(scan.p + DICT_SLOTS, stream);
+  if (d2h_one(ctr.p + 1, stream) || distinct + 1 >= DICT_MAX) return;
+  DBuf<uint32_t> rep(ctx, DICT_MAX + 1);
+  DBuf<uint16_t> code(ctx, n);
+  a.rep = rep.p;
+  a.code = code.p;
+  launch_dict_number(a, scan.p, stream);
+  launch_dict_code(a, stream);
+  if (d2h_one(ctr.p + 1, stream)) return;  // a string hash collision
+  col.code = std::move(code);
+  col.rep = std::move(rep);
+  col.ncode = uint32_t(distinct + 1);
+  col.dict = 1;
+}
+
+// Selected live-file ordinals from per-file flags (scan + compaction), then the call's timings.
+static std::vector<int64_t> select_flags(dr_state& st, DBuf<uint32_t>& flag) {
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  DBuf<uint8_t> scratch(ctx, scan_scratch_for(st.n_live));
+  DBuf<uint64_t> pos(ctx, st.n_live + 1);
+  launch_scan_u32(flag.p, pos.p, st.n_live, ss(scratch), stream);
+  const uint64_t nsel = st.n_live ? d2h_one(pos.p + st.n_live, stream) : 0;
+  DBuf<int64_t> sel(ctx, nsel);
+  launch_select(flag.p, pos.p, st.n_live, sel.p, stream);
+  std::vector<int64_t> out = d2h(sel.p, nsel, stream);
+  ctx->collect_timings();
+  return out;
+}
+
+static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& given) {
+  DR_STAGE("filter", st.ctx->stream);
+  check_program(given);
+  PatternPred compiled;
+  const dr_predicate& pred = compile_patterns(given, compiled) ? compiled.p : given;
+  dr_ctx* ctx = st.ctx;
+  ctx->begin_call();
+  ensure_ready(st);
+  hipStream_t stream = ctx->stream;
+  if (st.sources.empty()) fail(DR_E_INVALID_ARG, "state has no staged segment");
+  // the predicate's columns in the K5 cache (built for the ones not there yet)
+  auto find = [&](const std::string& name, int32_t type) -> dr_state::PvCol* {
+    for (auto& c : st.pv_cols)
+      if (c->name == name && c->type == type) return c.get();
+    return nullptr;
+  };
+  std::vector<std::pair<std::string, int32_t>> want;
+  for (int32_t c = 0; c < pred.ncols; ++c) {
+    std::pair<std::string, int32_t> k{pred.col_names[c], pred.col_types[c]};
+    if (!find(k.first, k.second) && std::find(want.begin(), want.end(), k) == want.end()) want.push_back(k);
+  }
+  if (!want.empty() && st.n_live) build_pv_columns(st, want);
+  FilterTypedArgs fa{};
+  fa.n_live = st.n_live;
+  fa.ncols = pred.ncols;
+  for (int32_t c = 0; c < pred.ncols; ++c) {
+    dr_state::PvCol* col = find(pred.col_names[c], pred.col_types[c]);
+    if (!col) {  // no live files: nothing was built
+      fa.cols[c].type = pred.col_types[c];
+      continue;
+    }
+    fa.cols[c] = pv_column(*col);
+  }
+  LeafPlan lp;
+  const bool force_generic = ctx->opt.filter_eval == 2;  // DR_OPT_FILTER_EVAL: k_filter_typed
+  if (!force_generic && leafify(pred, lp) && lp.prog.size() / 2 <= size_t(FL_MAXPROG) &&
+      lp.leaves.size() <= size_t(FL_MAXLEAF) && lp.i64.size() <= size_t(FL_MAXI64) &&
+      lp.str.size() <= size_t(FL_MAXSTR)) {
+    FilterLeafArgs la{};
+    la.n_live = st.n_live;
+    for (int32_t c = 0; c < pred.ncols; ++c) la.cols[c] = fa.cols[c];
+    std::vector<uint64_t> soff(lp.str.size() + 1, 0), s8(lp.str.size() + 1, 0);
+    std::string sbytes;
+    for (size_t q = 0; q < lp.str.size(); ++q) {
+      sbytes += lp.str[q];
+      soff[q + 1] = sbytes.size();
+      for (size_t k = 0; k < 8; ++k) s8[q] = (s8[q] << 8) | (k < lp.str[q].size() ? uint8_t(lp.str[q][k]) : 0u);
+    }
+    la.nprog = int32_t(lp.prog.size() / 2);
+    la.n_i64 = int32_t(lp.i64.size());
+    la.n_str = int32_t(lp.str.size());
+    la.nleaves = int32_t(lp.leaves.size());
+    std::vector<int32_t> ucol;
+    for (const FilterLeaf& f : lp.leaves)
+      if (std::find(ucol.begin(), ucol.end(), f.col) == ucol.end()) ucol.push_back(f.col);
+    la.nucol = ucol.size() <= size_t(FL_UCOLS) ? int32_t(ucol.size()) : 0;
+    for (int32_t u = 0; u < la.nucol; ++u) la.ucol[u] = ucol[size_t(u)];
+    for (FilterLeaf& f : lp.leaves) {
+      f.slot = -1;
+      for (int32_t u = 0; u < la.nucol; ++u)
+        if (la.ucol[u] == f.col) f.slot = u;
+      f.ctype = leaf_kind(la.cols[f.col].type);
+      la.extended |= f.ctype == DR_T_FLOAT || f.ctype == DR_T_DOUBLE || f.ctype == DR_T_DECIMAL || is_pattern_op(f.op);
+    }
+    const uint64_t ng = filter_leaf_groups(st.n_live);
+    DBuf<uint64_t> mask(ctx, uint64_t(filter_leaf_mask_words()) * ng), wg_off(ctx, ng + 1);
+    DBuf<uint32_t> wg_count(ctx, ng);
+    DBuf<uint8_t> scratch(ctx, scan_scratch_for(ng));
+    wg_count.zero(stream);
+    la.mask = mask.p;
+    la.wg_count = wg_count.p;
+    // the dictionary path when every column the leaves read has a dictionary and the leaf tables fit
+    std::vector<dr_state::PvCol*> ucols;
+    for (int32_t u = 0; u < la.nucol; ++u) ucols.push_back(find(pred.col_names[la.ucol[u]], pred.col_types[la.ucol[u]]));
+    bool use_dict = la.nucol > 0 && st.n_live && ctx->opt.filter_eval == 0;  // DR_OPT_FILTER_EVAL
+    for (dr_state::PvCol* c : ucols) {
+      if (!use_dict || !c) { use_dict = false; break; }
+      build_dict(st, *c);
+      use_dict = c->dict == 1;
+    }
+    std::vector<uint32_t> tab_off(lp.leaves.size() + 1, 0);
+    if (use_dict) {
+      for (size_t l = 0; l < lp.leaves.size(); ++l) tab_off[l + 1] = tab_off[l] + ucols[size_t(lp.leaves[l].slot)]->ncode;
+      use_dict = tab_off.back() <= FD_MAXTAB;
+    }
+    // the program, leaves and literals in one upload (each pageable upload is a staged copy of its own)
+    std::vector<uint8_t> blob;
+    auto put = [&](const void* src, size_t bytes) -> size_t {
+      const size_t at = (blob.size() + 15) & ~size_t(15);
+      blob.resize(at + bytes);
+      if (bytes) std::memcpy(blob.data() + at, src, bytes);
+      return at;
+    };
+    const size_t o_s8 = put(s8.data(), 8 * s8.size()), o_soff = put(soff.data(), 8 * soff.size());
+    const size_t o_prog = put(lp.prog.data(), 4 * lp.prog.size()), o_i64 = put(lp.i64.data(), 8 * lp.i64.size());
+    const size_t o_hi = put(lp.i64hi.data(), 8 * lp.i64hi.size());
+    const size_t o_leaves = put(lp.leaves.data(), sizeof(FilterLeaf) * lp.leaves.size());
+    const size_t o_toff = put(tab_off.data(), 4 * tab_off.size()), o_sb = put(sbytes.data(), sbytes.size());
+    DBuf<uint8_t> d_blob = upload(ctx, blob.data(), blob.size());
+    la.lit_s8 = reinterpret_cast<const uint64_t*>(d_blob.p + o_s8);
+    la.lit_str_off = reinterpret_cast<const uint64_t*>(d_blob.p + o_soff);
+    la.prog = reinterpret_cast<const int32_t*>(d_blob.p + o_prog);
+    la.lit_i64 = reinterpret_cast<const int64_t*>(d_blob.p + o_i64);
+    la.lit_hi = reinterpret_cast<const int64_t*>(d_blob.p + o_hi);
+    la.leaves = reinterpret_cast<const FilterLeaf*>(d_blob.p + o_leaves);
+    la.lit_str = d_blob.p + o_sb;
+    const uint32_t* d_toff = reinterpret_cast<const uint32_t*>(d_blob.p + o_toff);
+    DBuf<uint8_t> d_tab;
+    if (use_dict) {
+      d_tab = DBuf<uint8_t>(ctx, tab_off.back());
+      DictLeafArgs d{};
+      d.leaves = la.leaves;
+      d.nleaves = la.nleaves;
+      for (int32_t c = 0; c < pred.ncols; ++c) d.cols[c] = la.cols[c];
+      for (int32_t u = 0; u < la.nucol; ++u) {
+        d.rep[la.ucol[u]] = ucols[size_t(u)]->rep.p;
+        d.ncode[la.ucol[u]] = ucols[size_t(u)]->ncode;
+      }
+      d.tab_off = d_toff;
+      d.tab = d_tab.p;
+      d.lit_i64 = la.lit_i64;
+      d.lit_hi = la.lit_hi;
+      d.lit_s8 = la.lit_s8;
+      d.lit_str_off = la.lit_str_off;
+      d.lit_str = la.lit_str;
+      d.n_live = st.n_live;
+      launch_dict_leaf(d, tab_off.back(), stream);
+      FilterDictArgs f{};
+      f.n_live = st.n_live;
+      for (int32_t u = 0; u < la.nucol; ++u) f.code[u] = ucols[size_t(u)]->code.p;
+      f.nslot = la.nucol;
+      f.leaves = la.leaves;
+      f.nleaves = la.nleaves;
+      f.prog = la.prog;
+      f.nprog = la.nprog;
+      f.tab_off = d_toff;
+      f.tab = d_tab.p;
+      f.tab_bytes = tab_off.back();
+      f.mask = mask.p;
+      f.wg_count = wg_count.p;
+      launch_filter_dict(f, stream);
+    } else {
+      launch_filter_leaf(la, stream);
+    }
+    launch_scan_u32(wg_count.p, wg_off.p, ng, ss(scratch), stream);
+    const uint64_t nsel = ng ? d2h_one(wg_off.p + ng, stream) : 0;
+    DBuf<int64_t> sel(ctx, nsel);
+    if (nsel) launch_select_bits(mask.p, wg_off.p, st.n_live, sel.p, stream);
+    std::vector<int64_t> out = d2h(sel.p, nsel, stream);
+    ctx->collect_timings();
+    return out;
+  }
+  const std::vector<int32_t> ops = lower_program(pred);
+  std::vector<uint64_t> lit_off(size_t(pred.nlits) + 1, 0);
+  for (int32_t k = 0; k <= pred.nlits && pred.nlits; ++k) lit_off[size_t(k)] = uint64_t(pred.lit_str_off[k]);
+  const uint64_t lit_bytes = pred.nlits ? lit_off[size_t(pred.nlits)] : 0;
+  DBuf<int32_t> d_ops = upload(ctx, ops.data(), ops.size());
+  DBuf<int32_t> d_lt = upload(ctx, pred.lit_types, size_t(pred.nlits));
+  std::vector<int64_t> lit_lo(size_t(pred.nlits)), lit_hi(size_t(pred.nlits));
+  for (int32_t k = 0; k < pred.nlits; ++k) literal_words(pred, k, &lit_lo[size_t(k)], &lit_hi[size_t(k)]);
+  DBuf<int64_t> d_li = upload(ctx, lit_lo.data(), lit_lo.size()), d_lh = upload(ctx, lit_hi.data(), lit_hi.size());
+  DBuf<uint8_t> d_ln = upload(ctx, pred.lit_null, size_t(pred.nlits));
+  DBuf<uint64_t> d_lo = upload(ctx, lit_off.data(), lit_off.size());
+  DBuf<uint8_t> d_ls = upload(ctx, pred.lit_str_bytes, size_t(lit_bytes));
+  fa.nops = int32_t(ops.size() / 2);
+  fa.ops = d_ops.p;
+  fa.lit_types = d_lt.p;
+  fa.lit_i64 = d_li.p;
+  fa.lit_hi = d_lh.p;
+  fa.lit_null = d_ln.p;
+  fa.lit_str_off = d_lo.p;
+  fa.lit_str = d_ls.p;
+  DBuf<uint32_t> flag(ctx, st.n_live);
+  fa.flag = flag.p;
+  launch_filter_typed(fa, stream);
+  return select_flags(st, flag);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -4694,242 +4519,6 @@ static void write_checkpoint_part(dr_state& st, int32_t part, int32_t parts, uin
   ctx->collect_timings();
 }
 
-static std::vector<int64_t> select_flags(dr_state& st, DBuf<uint32_t>& flag);
-
-static PvColumn pv_column(const dr_state::PvCol& c) {
-  PvColumn p{};
-  p.type = c.type;
-  p.w32 = c.w32.p;
-  p.w64 = c.w64.p;
-  p.sptr = c.sptr.p;
-  p.slen = c.slen.p;
-  p.isnull = c.isnull.p;
-  p.s8 = c.s8.p;
-  p.w64hi = c.w64hi.p;
-  return p;
-}
-
-// Dictionary-encodes a typed partition column (k_dict_*): abandoned (dict = 0) past DICT_MAX - 1
-// distinct values, for a DECIMAL of precision > 18 (two-word values: the key is the low word) and
-// on a string hash collision.
-static void build_dict(dr_state& st, dr_state::PvCol& col) {
-  if (col.dict >= 0) return;
-  col.dict = 0;
-  const int base = col.type & 0xff;
-  if ((base == DR_T_DECIMAL && ((col.type >> 8) & 0xff) > 18) || !st.n_live) return;
-  dr_ctx* ctx = st.ctx;
-  hipStream_t stream = ctx->stream;
-  const uint64_t n = st.n_live;
-  DBuf<uint64_t> keys(ctx, DICT_SLOTS), scan(ctx, DICT_SLOTS + 1);
-  DBuf<uint32_t> tags(ctx, DICT_SLOTS), slot_code(ctx, DICT_SLOTS), occ(ctx, DICT_SLOTS);
-  DBuf<unsigned long long> ctr(ctx, 2);
-  DBuf<uint8_t> scratch(ctx, scan_scratch_for(DICT_SLOTS));
-  tags.zero(stream);
-  ctr.zero(stream);
-  PvDictArgs a{};
-  a.n = n;
-  a.col = pv_column(col);
-  a.key_tab = keys.p;
-  a.tag_tab = tags.p;
-  a.slot_code = slot_code.p;
-  a.ctr = ctr.p;
-  launch_dict_insert(a, stream);
-  launch_dict_occupied(a, occ.p, stream);
-  launch_scan_u32(occ.p, scan.p, DICT_SLOTS, ss(scratch), stream);
-  const uint64_t distinct = d2h_one(scan.p + DICT_SLOTS, stream);
-  if (d2h_one(ctr.p + 1, stream) || distinct + 1 >= DICT_MAX) return;
-  DBuf<uint32_t> rep(ctx, DICT_MAX + 1);
-  DBuf<uint16_t> code(ctx, n);
-  a.rep = rep.p;
-  a.code = code.p;
-  launch_dict_number(a, scan.p, stream);
-  launch_dict_code(a, stream);
-  if (d2h_one(ctr.p + 1, stream)) return;  // a string hash collision
-  col.code = std::move(code);
-  col.rep = std::move(rep);
-  col.ncode = uint32_t(distinct + 1);
-  col.dict = 1;
-}
-
-static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& given) {
-  DR_STAGE("filter", st.ctx->stream);
-  check_program(given);
-  PatternPred compiled;
-  const dr_predicate& pred = compile_patterns(given, compiled) ? compiled.p : given;
-  dr_ctx* ctx = st.ctx;
-  ctx->begin_call();
-  ensure_ready(st);
-  hipStream_t stream = ctx->stream;
-  if (st.sources.empty()) fail(DR_E_INVALID_ARG, "state has no staged segment");
-  // the predicate's columns in the K5 cache (built for the ones not there yet)
-  auto find = [&](const std::string& name, int32_t type) -> dr_state::PvCol* {
-    for (auto& c : st.pv_cols)
-      if (c->name == name && c->type == type) return c.get();
-    return nullptr;
-  };
-  std::vector<std::pair<std::string, int32_t>> want;
-  for (int32_t c = 0; c < pred.ncols; ++c) {
-    std::pair<std::string, int32_t> k{pred.col_names[c], pred.col_types[c]};
-    if (!find(k.first, k.second) && std::find(want.begin(), want.end(), k) == want.end()) want.push_back(k);
-  }
-  if (!want.empty() && st.n_live) build_pv_columns(st, want);
-  FilterTypedArgs fa{};
-  fa.n_live = st.n_live;
-  fa.ncols = pred.ncols;
-  for (int32_t c = 0; c < pred.ncols; ++c) {
-    dr_state::PvCol* col = find(pred.col_names[c], pred.col_types[c]);
-    if (!col) {  // no live files: nothing was built
-      fa.cols[c].type = pred.col_types[c];
-      continue;
-    }
-    fa.cols[c] = pv_column(*col);
-  }
-  LeafPlan lp;
-  const bool force_generic = ctx->opt.filter_eval == 2;  // DR_OPT_FILTER_EVAL: k_filter_typed
-  if (!force_generic && leafify(pred, lp) && lp.prog.size() / 2 <= filter_leaf_max_prog() &&
-      lp.leaves.size() <= filter_leaf_max_leaves() && lp.i64.size() <= filter_leaf_max_i64() &&
-      lp.str.size() <= filter_leaf_max_str()) {
-    FilterLeafArgs la{};
-    la.n_live = st.n_live;
-    for (int32_t c = 0; c < pred.ncols; ++c) la.cols[c] = fa.cols[c];
-    std::vector<uint64_t> soff(lp.str.size() + 1, 0), s8(lp.str.size() + 1, 0);
-    std::string sbytes;
-    for (size_t q = 0; q < lp.str.size(); ++q) {
-      sbytes += lp.str[q];
-      soff[q + 1] = sbytes.size();
-      for (size_t k = 0; k < 8; ++k) s8[q] = (s8[q] << 8) | (k < lp.str[q].size() ? uint8_t(lp.str[q][k]) : 0u);
-    }
-    la.nprog = int32_t(lp.prog.size() / 2);
-    la.n_i64 = int32_t(lp.i64.size());
-    la.n_str = int32_t(lp.str.size());
-    la.nleaves = int32_t(lp.leaves.size());
-    std::vector<int32_t> ucol;
-    for (const FilterLeaf& f : lp.leaves)
-      if (std::find(ucol.begin(), ucol.end(), f.col) == ucol.end()) ucol.push_back(f.col);
-    la.nucol = ucol.size() <= size_t(FL_UCOLS) ? int32_t(ucol.size()) : 0;
-    for (int32_t u = 0; u < la.nucol; ++u) la.ucol[u] = ucol[size_t(u)];
-    for (FilterLeaf& f : lp.leaves) {
-      f.slot = -1;
-      for (int32_t u = 0; u < la.nucol; ++u)
-        if (la.ucol[u] == f.col) f.slot = u;
-      f.ctype = leaf_kind(la.cols[f.col].type);
-      la.extended |= f.ctype == DR_T_FLOAT || f.ctype == DR_T_DOUBLE || f.ctype == DR_T_DECIMAL || is_pattern_op(f.op);
-    }
-    const uint64_t ng = filter_leaf_groups(st.n_live);
-    DBuf<uint64_t> mask(ctx, uint64_t(filter_leaf_mask_words()) * ng), wg_off(ctx, ng + 1);
-    DBuf<uint32_t> wg_count(ctx, ng);
-    DBuf<uint8_t> scratch(ctx, scan_scratch_for(ng));
-    wg_count.zero(stream);
-    la.mask = mask.p;
-    la.wg_count = wg_count.p;
-    // the dictionary path when every column the leaves read has a dictionary and the leaf tables fit
-    std::vector<dr_state::PvCol*> ucols;
-    for (int32_t u = 0; u < la.nucol; ++u) ucols.push_back(find(pred.col_names[la.ucol[u]], pred.col_types[la.ucol[u]]));
-    bool use_dict = la.nucol > 0 && st.n_live && ctx->opt.filter_eval == 0;  // DR_OPT_FILTER_EVAL
-    for (dr_state::PvCol* c : ucols) {
-      if (!use_dict || !c) { use_dict = false; break; }
-      build_dict(st, *c);
-      use_dict = c->dict == 1;
-    }
-    std::vector<uint32_t> tab_off(lp.leaves.size() + 1, 0);
-    if (use_dict) {
-      for (size_t l = 0; l < lp.leaves.size(); ++l) tab_off[l + 1] = tab_off[l] + ucols[size_t(lp.leaves[l].slot)]->ncode;
-      use_dict = tab_off.back() <= filter_dict_max_tab();
-    }
-    // the program, leaves and literals in one upload (each pageable upload is a staged copy of its own)
-    std::vector<uint8_t> blob;
-    auto put = [&](const void* src, size_t bytes) -> size_t {
-      const size_t at = (blob.size() + 15) & ~size_t(15);
-      blob.resize(at + bytes);
-      if (bytes) std::memcpy(blob.data() + at, src, bytes);
-      return at;
-    };
-    const size_t o_s8 = put(s8.data(), 8 * s8.size()), o_soff = put(soff.data(), 8 * soff.size());
-    const size_t o_prog = put(lp.prog.data(), 4 * lp.prog.size()), o_i64 = put(lp.i64.data(), 8 * lp.i64.size());
-    const size_t o_hi = put(lp.i64hi.data(), 8 * lp.i64hi.size());
-    const size_t o_leaves = put(lp.leaves.data(), sizeof(FilterLeaf) * lp.leaves.size());
-    const size_t o_toff = put(tab_off.data(), 4 * tab_off.size()), o_sb = put(sbytes.data(), sbytes.size());
-    DBuf<uint8_t> d_blob = upload(ctx, blob.data(), blob.size());
-    la.lit_s8 = reinterpret_cast<const uint64_t*>(d_blob.p + o_s8);
-    la.lit_str_off = reinterpret_cast<const uint64_t*>(d_blob.p + o_soff);
-    la.prog = reinterpret_cast<const int32_t*>(d_blob.p + o_prog);
-    la.lit_i64 = reinterpret_cast<const int64_t*>(d_blob.p + o_i64);
-    la.lit_hi = reinterpret_cast<const int64_t*>(d_blob.p + o_hi);
-    la.leaves = reinterpret_cast<const FilterLeaf*>(d_blob.p + o_leaves);
-    la.lit_str = d_blob.p + o_sb;
-    const uint32_t* d_toff = reinterpret_cast<const uint32_t*>(d_blob.p + o_toff);
-    DBuf<uint8_t> d_tab;
-    if (use_dict) {
-      d_tab = DBuf<uint8_t>(ctx, tab_off.back());
-      DictLeafArgs d{};
-      d.leaves = la.leaves;
-      d.nleaves = la.nleaves;
-      for (int32_t c = 0; c < pred.ncols; ++c) d.cols[c] = la.cols[c];
-      for (int32_t u = 0; u < la.nucol; ++u) {
-        d.rep[la.ucol[u]] = ucols[size_t(u)]->rep.p;
-        d.ncode[la.ucol[u]] = ucols[size_t(u)]->ncode;
-      }
-      d.tab_off = d_toff;
-      d.tab = d_tab.p;
-      d.lit_i64 = la.lit_i64;
-      d.lit_hi = la.lit_hi;
-      d.lit_s8 = la.lit_s8;
-      d.lit_str_off = la.lit_str_off;
-      d.lit_str = la.lit_str;
-      d.n_live = st.n_live;
-      launch_dict_leaf(d, tab_off.back(), stream);
-      FilterDictArgs f{};
-      f.n_live = st.n_live;
-      for (int32_t u = 0; u < la.nucol; ++u) f.code[u] = ucols[size_t(u)]->code.p;
-      f.nslot = la.nucol;
-      f.leaves = la.leaves;
-      f.nleaves = la.nleaves;
-      f.prog = la.prog;
-      f.nprog = la.nprog;
-      f.tab_off = d_toff;
-      f.tab = d_tab.p;
-      f.tab_bytes = tab_off.back();
-      f.mask = mask.p;
-      f.wg_count = wg_count.p;
-      launch_filter_dict(f, stream);
-    } else {
-      launch_filter_leaf(la, stream);
-    }
-    launch_scan_u32(wg_count.p, wg_off.p, ng, ss(scratch), stream);
-    const uint64_t nsel = ng ? d2h_one(wg_off.p + ng, stream) : 0;
-    DBuf<int64_t> sel(ctx, nsel);
-    if (nsel) launch_select_bits(mask.p, wg_off.p, st.n_live, sel.p, stream);
-    std::vector<int64_t> out = d2h(sel.p, nsel, stream);
-    ctx->collect_timings();
-    return out;
-  }
-  const std::vector<int32_t> ops = lower_program(pred);
-  std::vector<uint64_t> lit_off(size_t(pred.nlits) + 1, 0);
-  for (int32_t k = 0; k <= pred.nlits && pred.nlits; ++k) lit_off[size_t(k)] = uint64_t(pred.lit_str_off[k]);
-  const uint64_t lit_bytes = pred.nlits ? lit_off[size_t(pred.nlits)] : 0;
-  DBuf<int32_t> d_ops = upload(ctx, ops.data(), ops.size());
-  DBuf<int32_t> d_lt = upload(ctx, pred.lit_types, size_t(pred.nlits));
-  std::vector<int64_t> lit_lo(size_t(pred.nlits)), lit_hi(size_t(pred.nlits));
-  for (int32_t k = 0; k < pred.nlits; ++k) literal_words(pred, k, &lit_lo[size_t(k)], &lit_hi[size_t(k)]);
-  DBuf<int64_t> d_li = upload(ctx, lit_lo.data(), lit_lo.size()), d_lh = upload(ctx, lit_hi.data(), lit_hi.size());
-  DBuf<uint8_t> d_ln = upload(ctx, pred.lit_null, size_t(pred.nlits));
-  DBuf<uint64_t> d_lo = upload(ctx, lit_off.data(), lit_off.size());
-  DBuf<uint8_t> d_ls = upload(ctx, pred.lit_str_bytes, size_t(lit_bytes));
-  fa.nops = int32_t(ops.size() / 2);
-  fa.ops = d_ops.p;
-  fa.lit_types = d_lt.p;
-  fa.lit_i64 = d_li.p;
-  fa.lit_hi = d_lh.p;
-  fa.lit_null = d_ln.p;
-  fa.lit_str_off = d_lo.p;
-  fa.lit_str = d_ls.p;
-  DBuf<uint32_t> flag(ctx, st.n_live);
-  fa.flag = flag.p;
-  launch_filter_typed(fa, stream);
-  return select_flags(st, flag);
-}
-
-// Selected live-file ordinals from per-file flags (scan + compaction), then the call's timings.
 // ---------------------------------------------------------------------------------------------------
 // scan-side consumers: DeltaSourceSnapshot's (modificationTime, path) order and
 // TahoeFileIndex.listFiles' partition groups, computed over the resident state.
@@ -5090,20 +4679,6 @@ static void partition_groups(dr_state& st, const int64_t* rows, int64_t nrows, s
   order = to_host_positions(keys, n, stream);
   off = d2h(starts.p, ng, stream);
   off.push_back(int64_t(n));
-}
-
-static std::vector<int64_t> select_flags(dr_state& st, DBuf<uint32_t>& flag) {
-  dr_ctx* ctx = st.ctx;
-  hipStream_t stream = ctx->stream;
-  DBuf<uint8_t> scratch(ctx, scan_scratch_for(st.n_live));
-  DBuf<uint64_t> pos(ctx, st.n_live + 1);
-  launch_scan_u32(flag.p, pos.p, st.n_live, ss(scratch), stream);
-  const uint64_t nsel = st.n_live ? d2h_one(pos.p + st.n_live, stream) : 0;
-  DBuf<int64_t> sel(ctx, nsel);
-  launch_select(flag.p, pos.p, st.n_live, sel.p, stream);
-  std::vector<int64_t> out = d2h(sel.p, nsel, stream);
-  ctx->collect_timings();
-  return out;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -565,8 +565,6 @@ __device__ int cmp_sv(const SV& a, const SV& b) {
   return x == y ? 0 : (x < y ? -1 : 1);
 }
 
-constexpr int PV_STACK = 32;
-
 // ---- k_pv_extract --------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_pv_extract(PvExtractArgs a) {
   const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1003,7 +1001,6 @@ __device__ __forceinline__ void load_col4(const FilterLeafArgs& a, const PvColum
 // front and each leaf reads its column's slot (fixed by the host: a scalar branch picks it);
 // otherwise each leaf loads its own column. A wave adds its selected count to its tile's (zeroed)
 // count: no barrier per tile.
-constexpr int FL_MAXPROG = 128, FL_MAXLEAF = 64, FL_MAXI64 = 1024, FL_MAXSTR = 256;
 template <bool X>
 __device__ __forceinline__ void filter_leaf_tiles(const FilterLeafArgs& a) {
   __shared__ int32_t sprog[2 * FL_MAXPROG];
@@ -1253,7 +1250,6 @@ __global__ void __launch_bounds__(256) k_dict_leaf(DictLeafArgs a, uint32_t tota
 
 // The per-file pass over codes: tiles of FL_FILES files, FL_PER per lane; every leaf is one LDS
 // byte read per file.
-constexpr uint32_t FD_MAXTAB = 32768;
 __global__ void __launch_bounds__(FL_T) k_filter_dict(FilterDictArgs a) {
   __shared__ int32_t sprog[2 * FL_MAXPROG];
   __shared__ FilterLeaf sleaf[FL_MAXLEAF];
@@ -1446,16 +1442,13 @@ __global__ void __launch_bounds__(256) k_record_hash(RecordHashArgs a) {
 
 static inline unsigned g256(uint64_t n) { return unsigned((n + 255) / 256); }
 
-uint32_t filter_max_cols() { return PV_MAXC; }
-uint32_t filter_max_stack() { return dev::PV_STACK; }
-
 void launch_pv_extract(const PvExtractArgs& a, hipStream_t st) {
   if (a.n_live) DR_LAUNCH(dev::k_pv_extract, dim3(g256(a.n_live)), dim3(256), 0, st, a);
 }
 uint64_t filter_leaf_groups(uint64_t n) { return (n + dev::FL_FILES - 1) / dev::FL_FILES; }
 uint32_t filter_leaf_mask_words() { return dev::FL_FILES / 64; }
 void launch_filter_leaf(const FilterLeafArgs& a, hipStream_t st) {
-  if (a.nprog > dev::FL_MAXPROG || a.nleaves > dev::FL_MAXLEAF)
+  if (a.nprog > FL_MAXPROG || a.nleaves > FL_MAXLEAF)
     throw std::runtime_error("filter program too long for the leaf kernel");
   // persistent: four resident workgroups per CU (k_filter_leaf 124 VGPRs: 4 waves/SIMD; k_filter_leaf_x 129: 3), each walking tiles grid-stride
   const unsigned g = unsigned(DR_FL_GRID ? std::min<uint64_t>(filter_leaf_groups(a.n_live), 256 * DR_FL_GRID)
@@ -1464,7 +1457,6 @@ void launch_filter_leaf(const FilterLeafArgs& a, hipStream_t st) {
   if (a.extended) DR_LAUNCH(dev::k_filter_leaf_x, dim3(g), dim3(dev::FL_T), 0, st, a);
   else DR_LAUNCH(dev::k_filter_leaf, dim3(g), dim3(dev::FL_T), 0, st, a);
 }
-uint32_t filter_leaf_max_prog() { return dev::FL_MAXPROG; }
 void launch_dict_insert(const PvDictArgs& a, hipStream_t st) {
   const uint64_t per = uint64_t(dev::DICT_T) * dev::DICT_PER;
   if (a.n) DR_LAUNCH(dev::k_dict_insert, dim3(unsigned((a.n + per - 1) / per)), dim3(dev::DICT_T), 0, st, a);
@@ -1481,16 +1473,12 @@ void launch_dict_code(const PvDictArgs& a, hipStream_t st) {
 void launch_dict_leaf(const DictLeafArgs& a, uint32_t total, hipStream_t st) {
   if (total) DR_LAUNCH(dev::k_dict_leaf, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, a, total);
 }
-uint32_t filter_dict_max_tab() { return dev::FD_MAXTAB; }
 void launch_filter_dict(const FilterDictArgs& a, hipStream_t st) {
-  if (a.nprog > dev::FL_MAXPROG || a.nleaves > dev::FL_MAXLEAF || a.tab_bytes > dev::FD_MAXTAB)
+  if (a.nprog > FL_MAXPROG || a.nleaves > FL_MAXLEAF || a.tab_bytes > FD_MAXTAB)
     throw std::runtime_error("filter program too long for the dictionary kernel");
   const unsigned g = unsigned(std::min<uint64_t>(filter_leaf_groups(a.n_live), 256 * 8));
   if (a.n_live) DR_LAUNCH(dev::k_filter_dict, dim3(g), dim3(dev::FL_T), 0, st, a);
 }
-uint32_t filter_leaf_max_i64() { return dev::FL_MAXI64; }
-uint32_t filter_leaf_max_str() { return dev::FL_MAXSTR; }
-uint32_t filter_leaf_max_leaves() { return dev::FL_MAXLEAF; }
 void launch_select_bits(const uint64_t* mask, const uint64_t* wg_off, uint64_t n, int64_t* out, hipStream_t st) {
   if (n) DR_LAUNCH(dev::k_select_bits, dim3(unsigned(filter_leaf_groups(n))), dim3(dev::FL_T), 0, st, mask, wg_off, n, out);
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <cstdint>
+#include "filter_plan.h"
 
 namespace dr {
 
@@ -388,61 +389,8 @@ void launch_verdict_collect(const uint8_t* verdict, const uint32_t* send_idx, ui
 // Two kernels: k_pv_extract builds, once per state and partition column, the column's values cast to
 // the column type for every live AddFile (the state's K5 cache); k_filter_typed evaluates a
 // predicate program over those typed columns, so a filter reads 4-12 B per file and column.
-constexpr int PV_MAXC = 16;
-
-// Floating-point order keys (SQLOrderingUtil.compareDoubles / compareFloats: -0.0 = 0.0, NaN = NaN,
-// NaN above +Infinity): the bits with every NaN canonical and -0.0 turned into +0.0, then the magnitude
-// bits of negative values flipped, so the signed integer order of the keys is that order. The device
-// applies them when it loads a FLOAT / DOUBLE cache value (the cache keeps the raw bits: the
-// checkpoint writer reads them), the host to every literal (engine.hip). Each is its own inverse on
-// canonical values.
-#if defined(__HIPCC__)
-#define DR_HD __host__ __device__
-#else
-#define DR_HD
-#endif
-DR_HD inline int64_t fp_key64(uint64_t bits) {
-  if ((bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) bits = 0x7ff8000000000000ull;
-  if (bits == 0x8000000000000000ull) bits = 0;
-  const int64_t k = int64_t(bits);
-  return k ^ ((k >> 63) & 0x7fffffffffffffffll);
-}
-DR_HD inline int64_t fp_key32(uint32_t bits) {
-  if ((bits & 0x7fffffffu) > 0x7f800000u) bits = 0x7fc00000u;
-  if (bits == 0x80000000u) bits = 0;
-  const int32_t k = int32_t(bits);
-  return int64_t(k ^ ((k >> 31) & 0x7fffffff));
-}
-// The 64-bit key of the binary32 value whose 32-bit key is `k32`: the value widened exactly to
-// binary64 (a float column compared with a double literal), in integer arithmetic (subnormals
-// included, whatever the denormal mode).
-DR_HD inline int64_t fp_key_widen(int64_t k32) {
-  const int32_t k = int32_t(k32);
-  const uint32_t b = uint32_t(k ^ ((k >> 31) & 0x7fffffff));
-  const uint64_t sign = uint64_t(b >> 31) << 63;
-  int32_t e = int32_t((b >> 23) & 0xffu);
-  uint32_t m = b & 0x7fffffu;
-  uint64_t d;
-  if (e == 255) {
-    d = sign | 0x7ff0000000000000ull | (uint64_t(m) << 29);
-  } else if (e == 0 && m == 0) {
-    d = sign;
-  } else {
-    if (e == 0) {  // subnormal: normalise
-      const int sh = __builtin_clz(m) - 8;
-      m = (m << sh) & 0x7fffffu;
-      e = 1 - sh;
-    }
-    d = sign | (uint64_t(e + 896) << 52) | (uint64_t(m) << 29);
-  }
-  return fp_key64(d);
-}
-// The kind a leaf evaluates a column as: BINARY as STRING (bytes), TIMESTAMP as LONG (one 64-bit
-// integer); FLOAT / DOUBLE through their keys; DECIMAL as two words (w64 unsigned under w64hi).
-DR_HD inline int32_t leaf_kind(int32_t type) {
-  const int32_t b = type & 0xff;
-  return b == 10 /* DR_T_BINARY */ ? 0 /* DR_T_STRING */ : b == 9 /* DR_T_TIMESTAMP */ ? 4 /* DR_T_LONG */ : b;
-}
+// FilterLeaf, the order keys, the plan opcodes and the limits shared with the host-only planner
+// (pred_plan.cpp) are in filter_plan.h.
 struct PvColumn {
   int32_t type;        // dr_pred_type (DECIMAL: | precision << 8 | scale << 16)
   uint32_t* w32;       // BYTE / SHORT / INT / DATE (days) / BOOLEAN (0/1) / FLOAT (bits)
@@ -504,22 +452,6 @@ struct FilterTypedArgs {
   uint32_t* flag;                // [n_live] 1 = selected
   const int64_t* lit_hi;         // DECIMAL literals: the high word (others: 0)
 };
-// Leaf form of a predicate (engine.hip leafify): every leaf compares one partition column with
-// literals -- col op lit, col IN (lits), col IS [NOT] NULL -- and AND / OR / NOT combine their
-// three-valued results on a 2-bit-per-entry stack held in one register.
-struct FilterLeaf {
-  int32_t col;       // predicate column
-  int32_t op;        // DR_OP_EQ .. DR_OP_GE, DR_OP_NSEQ, DR_OP_IN, DR_OP_ISNULL, DR_OP_ISNOTNULL,
-                     // DR_OP_STARTSWITH .. DR_OP_LIKE (literal `lit`: the needle / like_lane.h's program)
-  int32_t lit;       // literal index (comparisons) or first entry of the sorted set (IN)
-  int32_t nlit;      // IN: entries in the set
-  int32_t lit_null;  // comparisons: the literal is NULL; IN: the list holds a NULL
-  int32_t pad;       // IN over integers: 1 = a bitmap (literals [min, words, bits...]); a FLOAT column
-                     // against DOUBLE literals: 2 = widen the value's key (fp_key_widen) first
-  int32_t slot;      // k_filter_leaf: the preloaded column slot holding `col` (-1: loaded per leaf)
-  int32_t ctype;     // leaf_kind of the column's dr_pred_type
-};
-enum : int32_t { LEAF_OP_LEAF = 0, LEAF_OP_AND = 1, LEAF_OP_OR = 2, LEAF_OP_NOT = 3 };
 struct FilterLeafArgs {
   uint64_t n_live;
   PvColumn cols[PV_MAXC];
@@ -539,21 +471,12 @@ struct FilterLeafArgs {
   const int64_t* lit_hi;         // [n_i64] DECIMAL literals' high words (read by decimal leaves only)
   int32_t extended;              // a leaf reads a FLOAT / DOUBLE / DECIMAL column or is a string pattern: k_filter_leaf_x
 };
-constexpr int FL_UCOLS = 4;
-uint32_t filter_leaf_max_prog();
-uint32_t filter_leaf_max_i64();   // literals k_filter_leaf holds in LDS (more: k_filter_typed)
-uint32_t filter_leaf_max_str();
-uint32_t filter_leaf_max_leaves();
 // 1024-file tiles of k_filter_leaf: the sizes of `mask` (x16) and `wg_count`
 uint64_t filter_leaf_groups(uint64_t n_live);
 uint32_t filter_leaf_mask_words();  // mask words per tile
 void launch_filter_leaf(const FilterLeafArgs& a, hipStream_t st);
 // out[wg_off[g] + rank] = ordinal of every selected file (wg_off: exclusive scan of wg_count)
 void launch_select_bits(const uint64_t* mask, const uint64_t* wg_off, uint64_t n, int64_t* out, hipStream_t st);
-// device-only opcodes of the lowered program (engine.hip lower_program): an IN list is folded
-// one element at a time into an accumulator slot above its value
-enum : int32_t { FILTER_OP_IN_START = 100, FILTER_OP_IN_STEP = 101, FILTER_OP_IN_END = 102 };
-uint32_t filter_max_cols();
 // ---- K5 dictionary path: each partition column's distinct values get u16 codes (code 0: NULL), a
 // leaf becomes a table over its column's codes, and the per-file pass reads 2 bytes per column.
 constexpr uint32_t DICT_SLOTS = 1u << 17;   // global hash table (load <= 1/2)
@@ -602,9 +525,7 @@ struct FilterDictArgs {
   uint64_t* mask;
   uint32_t* wg_count;
 };
-uint32_t filter_dict_max_tab();   // leaf-table bytes the dictionary kernel holds in LDS
 void launch_filter_dict(const FilterDictArgs& a, hipStream_t st);
-uint32_t filter_max_stack();
 void launch_pv_extract(const PvExtractArgs& a, hipStream_t st);
 void launch_filter_typed(const FilterTypedArgs& a, hipStream_t st);
 void launch_rep0_flags(const uint8_t* rep, uint64_t n, uint32_t* f, hipStream_t st);

@@ -1,0 +1,425 @@
+// K5 predicate planner, host only (pred_plan.h says what each function is for).
+#include "pred_plan.h"
+
+#include <algorithm>
+#include <cstring>
+#include <functional>
+#include <utility>
+
+#include "like_lane.h"
+
+namespace dr {
+
+// Which literals a column may be compared with: a FLOAT, DOUBLE, TIMESTAMP, DECIMAL or BINARY column
+// (the type codes from DR_T_FLOAT up) takes literals of its own type only (a decimal's precision and
+// scale included), a FLOAT column also a DOUBLE literal (the value is widened), and a literal of one
+// of those types fits no other column. STRING, the integer kinds, DATE and BOOLEAN among themselves
+// are not checked.
+static bool new_pred_type(int32_t t) { return (t & 0xff) >= DR_T_FLOAT; }
+static bool lit_fits(int32_t ctype, int32_t ltype) {
+  if (!new_pred_type(ctype) && !new_pred_type(ltype)) return true;
+  return ctype == ltype || (ctype == DR_T_FLOAT && ltype == DR_T_DOUBLE);
+}
+
+// A DECIMAL literal: 16 bytes, little-endian two's complement, in the string bytes.
+static void decimal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t* hi) {
+  uint64_t w[2];
+  std::memcpy(w, p.lit_str_bytes + p.lit_str_off[k], 16);
+  *lo = int64_t(w[0]);
+  *hi = int64_t(w[1]);
+}
+
+void literal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t* hi) {
+  *lo = p.lit_i64[k];
+  *hi = 0;
+  if (p.lit_null[k]) return;
+  const int base = p.lit_types[k] & 0xff;
+  if (base == DR_T_FLOAT) *lo = fp_key32(uint32_t(p.lit_i64[k]));
+  else if (base == DR_T_DOUBLE) *lo = fp_key64(uint64_t(p.lit_i64[k]));
+  else if (base == DR_T_DECIMAL) decimal_words(p, k, lo, hi);
+}
+
+// ---- string patterns (DR_OP_STARTSWITH .. DR_OP_LIKE) ------------------------------------------------
+static const char* pattern_op_name(int op) {
+  return op == DR_OP_STARTSWITH ? "STARTSWITH" : op == DR_OP_ENDSWITH ? "ENDSWITH" : op == DR_OP_CONTAINS ? "CONTAINS" : "LIKE";
+}
+static std::string pred_op_text(const dr_predicate& p, int32_t k) {
+  const int op = p.ops[k].opcode, arg = p.ops[k].arg;
+  if (op == DR_OP_COL) return fmt("partition column %s of type %d", p.col_names[arg], p.col_types[arg]);
+  if (op == DR_OP_LIT) return p.lit_null[arg] ? std::string("a NULL literal") : fmt("literal %d of type %d", arg, p.lit_types[arg]);
+  return fmt("the result of op %d (opcode %d)", k, op);
+}
+static lk::LikeCompiled compile_like(const dr_predicate& p, int32_t lit, int32_t escape) {
+  const int64_t b = p.lit_str_off[lit], e = p.lit_str_off[lit + 1];
+  return lk::like_compile(p.lit_str_bytes + b, size_t(e - b), uint32_t(escape));
+}
+// Pattern op k over the operands rooted at ops vk (value) and pk (pattern): the value a STRING
+// partition column, the pattern a STRING or NULL literal, a LIKE pattern well-formed. The pattern is
+// the last operand and, being a literal, a single op: it is op k - 1, where compile_patterns reads it.
+static void check_pattern_op(const dr_predicate& p, int32_t k, int32_t vk, int32_t pk) {
+  const int op = p.ops[k].opcode;
+  const char* name = pattern_op_name(op);
+  if (p.ops[vk].opcode != DR_OP_COL || p.col_types[p.ops[vk].arg] != DR_T_STRING)
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the value must be a STRING partition column, found %s", k, name,
+                               pred_op_text(p, vk).c_str()));
+  const int32_t l = p.ops[pk].arg;
+  if (p.ops[pk].opcode != DR_OP_LIT || (!p.lit_null[l] && p.lit_types[l] != DR_T_STRING))
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the pattern must be a STRING or NULL literal, found %s", k, name,
+                               pred_op_text(p, pk).c_str()));
+  if (!p.lit_null[l] && (!p.lit_str_off || p.lit_str_off[l] < 0 || p.lit_str_off[l + 1] < p.lit_str_off[l] ||
+                         (p.lit_str_off[l + 1] > p.lit_str_off[l] && !p.lit_str_bytes)))
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): literal %d has no valid bytes", k, name, l));
+  if (op != DR_OP_LIKE) return;
+  const int32_t esc = p.ops[k].arg;
+  if (esc < 1 || esc > 0xFFFF || (esc >= 0xD800 && esc <= 0xDFFF))
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (LIKE): the escape character (arg %d) must be a code point in 1..0xFFFF and no surrogate", k, esc));
+  if (p.lit_null[l]) return;
+  const lk::LikeCompiled c = compile_like(p, l, esc);
+  if (!c.error.empty()) fail(DR_E_INVALID_ARG, fmt("predicate op %d (LIKE): %s", k, c.error.c_str()));
+}
+
+bool compile_patterns(const dr_predicate& p, PatternPred& out) {
+  bool any = false;
+  for (int32_t k = 0; k < p.nops; ++k) any |= p.ops[k].opcode == DR_OP_LIKE && !p.lit_null[p.ops[k - 1].arg];
+  if (!any) return false;
+  const size_t nl = size_t(p.nlits);
+  out.ops.assign(p.ops, p.ops + p.nops);
+  out.lit_types.assign(p.lit_types, p.lit_types + nl);
+  out.lit_i64.assign(p.lit_i64, p.lit_i64 + nl);
+  out.lit_null.assign(p.lit_null, p.lit_null + nl);
+  out.lit_str_off.assign(p.lit_str_off, p.lit_str_off + nl + 1);
+  if (out.lit_str_off.back() > 0) out.bytes.assign(p.lit_str_bytes, p.lit_str_bytes + out.lit_str_off.back());
+  for (int32_t k = 0; k < p.nops; ++k) {
+    if (p.ops[k].opcode != DR_OP_LIKE || p.lit_null[p.ops[k - 1].arg]) continue;
+    const lk::LikeCompiled c = compile_like(p, p.ops[k - 1].arg, p.ops[k].arg);
+    out.ops[size_t(k) - 1].arg = int32_t(out.lit_types.size());
+    out.ops[size_t(k)].opcode = c.kind == lk::LIKE_EQ ? DR_OP_EQ : c.kind == lk::LIKE_STARTSWITH ? DR_OP_STARTSWITH
+                              : c.kind == lk::LIKE_ENDSWITH ? DR_OP_ENDSWITH : c.kind == lk::LIKE_CONTAINS ? DR_OP_CONTAINS
+                              : DR_OP_LIKE;
+    out.ops[size_t(k)].arg = 0;
+    out.lit_types.push_back(DR_T_STRING);
+    out.lit_i64.push_back(0);
+    out.lit_null.push_back(0);
+    out.bytes.insert(out.bytes.end(), c.text.begin(), c.text.end());
+    out.lit_str_off.push_back(int64_t(out.bytes.size()));
+  }
+  out.p = p;
+  out.p.ops = out.ops.data();
+  out.p.nlits = int32_t(out.lit_types.size());
+  out.p.lit_types = out.lit_types.data();
+  out.p.lit_i64 = out.lit_i64.data();
+  out.p.lit_null = out.lit_null.data();
+  out.p.lit_str_off = out.lit_str_off.data();
+  out.p.lit_str_bytes = out.bytes.data();
+  return true;
+}
+
+// ---- the program as a tree ---------------------------------------------------------------------------
+// The values an op takes off the stack, every opcode listed; -1: no such opcode, or an IN list of a
+// negative length.
+static int64_t arity(const dr_pred_op& o) {
+  switch (o.opcode) {
+    case DR_OP_COL: case DR_OP_LIT:
+      return 0;
+    case DR_OP_ISNULL: case DR_OP_ISNOTNULL: case DR_OP_NOT:
+      return 1;
+    case DR_OP_EQ: case DR_OP_NE: case DR_OP_LT: case DR_OP_LE: case DR_OP_GT: case DR_OP_GE: case DR_OP_NSEQ:
+    case DR_OP_AND: case DR_OP_OR:
+    case DR_OP_STARTSWITH: case DR_OP_ENDSWITH: case DR_OP_CONTAINS: case DR_OP_LIKE:
+      return 2;
+    case DR_OP_IN:
+      return o.arg < 0 ? -1 : int64_t(o.arg) + 1;
+    default:
+      return -1;
+  }
+}
+struct Kids {  // the n ops whose values an op takes, in operand order
+  const int32_t* b;
+  size_t n;
+  int32_t operator[](size_t q) const { return b[q]; }
+};
+// Postfix -> tree: every op's operands are whole subtrees, named by their last (root) op. It stops at
+// the first op that has no arity or finds too few values below it; check_program turns that into
+// the error, and a program that passed it has none (bad == nops, left == 1).
+struct Tree {
+  // one block: at[nops + 1], then kid[nops] (an op is the operand of at most one other), then the
+  // stack the walk uses; op k's operands are kid[at[k]] .. kid[at[k + 1])
+  std::vector<int32_t> buf;
+  int32_t nops;
+  int32_t bad;   // the op it stopped at (nops: none)
+  size_t left;   // values on the stack there
+  Kids kids(int32_t k) const {
+    const int32_t* at = buf.data();
+    return Kids{at + nops + 1 + at[k], size_t(at[k + 1] - at[k])};
+  }
+};
+static Tree tree_of(const dr_predicate& p) {
+  const size_t nops = size_t(p.nops);
+  Tree t{std::vector<int32_t>(3 * nops + 1), p.nops, p.nops, 0};
+  int32_t *at = t.buf.data(), *kid = at + nops + 1, *stack = kid + nops;
+  size_t depth = 0;
+  for (int32_t k = 0; k < p.nops; ++k) {
+    const int64_t n = arity(p.ops[k]);
+    if (n < 0 || int64_t(depth) < n) {
+      t.bad = k;
+      break;
+    }
+    depth -= size_t(n);
+    std::copy(stack + depth, stack + depth + n, kid + at[k]);
+    at[k + 1] = at[k] + int32_t(n);
+    stack[depth++] = k;
+  }
+  t.left = depth;
+  return t;
+}
+
+void check_program(const dr_predicate& p) {
+  if (p.ncols < 0 || p.ncols > PV_MAXC)
+    fail(DR_E_UNSUPPORTED, fmt("at most %u partition columns per predicate", unsigned(PV_MAXC)));
+  if (p.nops <= 0 || !p.ops) fail(DR_E_INVALID_ARG, "empty predicate program");
+  if (p.ncols && (!p.col_names || !p.col_types)) fail(DR_E_INVALID_ARG, "missing partition columns");
+  if (p.nlits && (!p.lit_types || !p.lit_i64 || !p.lit_null || !p.lit_str_off))
+    fail(DR_E_INVALID_ARG, "missing literals");
+  // a type code: STRING .. BINARY bare, DECIMAL | p << 8 | s << 16 with 1 <= p <= 38, s <= p
+  auto type_ok = [](int32_t t) {
+    if (t < 0) return false;
+    if ((t & 0xff) != DR_T_DECIMAL) return t <= DR_T_BINARY;
+    const int32_t prec = (t >> 8) & 0xff, scale = t >> 16;
+    return prec >= 1 && prec <= 38 && scale <= prec;
+  };
+  for (int32_t c = 0; c < p.ncols; ++c)
+    if (!type_ok(p.col_types[c]) || !p.col_names[c])
+      fail(DR_E_UNSUPPORTED, "unsupported partition column type");
+  for (int32_t k = 0; k < p.nlits; ++k) {
+    if (p.lit_null[k]) continue;
+    const int32_t t = p.lit_types[k];
+    if (!type_ok(t)) fail(DR_E_INVALID_ARG, fmt("predicate literal %d has no valid type (code %d)", k, t));
+    if ((t & 0xff) != DR_T_DECIMAL) continue;
+    if (!p.lit_str_bytes || p.lit_str_off[k] < 0 || p.lit_str_off[k + 1] - p.lit_str_off[k] != 16)
+      fail(DR_E_INVALID_ARG, fmt("decimal literal %d must be 16 bytes (little-endian two's complement)", k));
+    int64_t lo, hi;
+    decimal_words(p, k, &lo, &hi);
+    // (assembled unsigned: shifting a negative high word left is undefined)
+    const __int128 v = __int128(((unsigned __int128)uint64_t(hi) << 64) | uint64_t(lo));
+    unsigned __int128 lim = 1;
+    for (int32_t d = 0; d < ((t >> 8) & 0xff); ++d) lim *= 10;
+    if ((v < 0 ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v) >= lim)
+      fail(DR_E_INVALID_ARG, fmt("decimal literal %d does not fit precision %d", k, (t >> 8) & 0xff));
+  }
+  // a literal compared with a column must be of a kind the column takes (lit_fits)
+  auto fits = [&](int32_t ck, int32_t lk) {
+    if (p.ops[ck].opcode != DR_OP_COL || p.ops[lk].opcode != DR_OP_LIT) return;
+    const int32_t c = p.ops[ck].arg, l = p.ops[lk].arg;
+    if (!p.lit_null[l] && !lit_fits(p.col_types[c], p.lit_types[l]))
+      fail(DR_E_INVALID_ARG, fmt("predicate literal %d (type %d) does not fit partition column %s (type %d)", l,
+                                 p.lit_types[l], p.col_names[c], p.col_types[c]));
+  };
+  // op by op, so that the first fault in program order is the one reported: its indices, its place in
+  // the tree, then its operands
+  const Tree t = tree_of(p);
+  for (int32_t k = 0; k < p.nops; ++k) {
+    const int op = p.ops[k].opcode, arg = p.ops[k].arg;
+    if (op == DR_OP_COL && (arg < 0 || arg >= p.ncols)) fail(DR_E_INVALID_ARG, "predicate column index out of range");
+    if (op == DR_OP_LIT && (arg < 0 || arg >= p.nlits)) fail(DR_E_INVALID_ARG, "predicate literal index out of range");
+    if (k == t.bad)
+      fail(DR_E_INVALID_ARG, op == DR_OP_IN ? "predicate stack underflow (IN)"
+                             : arity(p.ops[k]) < 0 ? fmt("unknown predicate opcode %d", op) : "predicate stack underflow");
+    const Kids ch = t.kids(k);
+    if (is_pattern_op(op)) check_pattern_op(p, k, ch[0], ch[1]);
+    if (op >= DR_OP_EQ && op <= DR_OP_NSEQ) {
+      fits(ch[0], ch[1]);
+      fits(ch[1], ch[0]);
+    } else if (op == DR_OP_IN) {
+      for (size_t q = 1; q < ch.n; ++q) fits(ch[0], ch[q]);
+    }
+  }
+  if (t.left != 1) fail(DR_E_INVALID_ARG, "predicate program must leave one value");
+}
+
+std::vector<int32_t> lower_program(const dr_predicate& p) {
+  const Tree t = tree_of(p);
+  std::vector<int32_t> out;
+  int depth = 0, max_depth = 0;
+  auto put = [&](int32_t op, int32_t arg, int delta) {
+    out.push_back(op);
+    out.push_back(arg);
+    depth += delta;
+    max_depth = std::max(max_depth, depth);
+  };
+  std::function<void(int32_t)> emit = [&](int32_t k) {
+    const int op = p.ops[k].opcode, arg = p.ops[k].arg;
+    const Kids ch = t.kids(k);
+    if (op == DR_OP_IN) {
+      emit(ch[0]);
+      put(FILTER_OP_IN_START, 0, +1);
+      for (size_t q = 1; q < ch.n; ++q) {
+        emit(ch[q]);
+        put(FILTER_OP_IN_STEP, 0, -1);
+      }
+      put(FILTER_OP_IN_END, 0, -1);
+      return;
+    }
+    for (size_t q = 0; q < ch.n; ++q) emit(ch[q]);
+    put(op, arg, 1 - int(ch.n));
+  };
+  emit(p.nops - 1);
+  if (max_depth > PV_STACK) fail(DR_E_UNSUPPORTED, "predicate program too deep");
+  return out;
+}
+
+bool leafify(const dr_predicate& p, LeafPlan& L) {
+  const Tree t = tree_of(p);
+  auto is_col = [&](int32_t k) { return p.ops[k].opcode == DR_OP_COL; };
+  auto is_lit = [&](int32_t k) { return p.ops[k].opcode == DR_OP_LIT; };
+  auto is_str = [](int32_t t) { return leaf_kind(t) == DR_T_STRING; };
+  // string (and binary) columns with literals of bytes, others numeric; the new types by lit_fits
+  auto kind_ok = [&](int32_t col, int32_t lit) {
+    return is_str(p.col_types[col]) == is_str(p.lit_types[lit]) && lit_fits(p.col_types[col], p.lit_types[lit]);
+  };
+  // a FLOAT column's literal as the leaf compares it: a DOUBLE literal's key as it is (the leaf widens
+  // the value, pad = 2), and then a FLOAT literal's key widened like the value
+  auto fp_word = [&](int32_t lit, bool widen) {
+    int64_t lo, hi;
+    literal_words(p, lit, &lo, &hi);
+    return widen && p.lit_types[lit] == DR_T_FLOAT ? fp_key_widen(lo) : lo;
+  };
+  auto slot = [&](int32_t lit) {
+    int64_t lo, hi;
+    literal_words(p, lit, &lo, &hi);
+    L.i64.push_back(lo);
+    L.i64hi.push_back(hi);
+    if (is_str(p.lit_types[lit]))
+      L.str.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[lit],
+                         size_t(p.lit_str_off[lit + 1] - p.lit_str_off[lit]));
+    else L.str.emplace_back();
+    return int32_t(L.i64.size() - 1);
+  };
+  int depth = 0, max_depth = 0;
+  std::function<bool(int32_t)> emit = [&](int32_t k) -> bool {
+    const int op = p.ops[k].opcode;
+    const Kids ch = t.kids(k);
+    auto push_leaf = [&](const FilterLeaf& f) {
+      L.prog.push_back(LEAF_OP_LEAF);
+      L.prog.push_back(int32_t(L.leaves.size()));
+      L.leaves.push_back(f);
+      max_depth = std::max(max_depth, ++depth);
+      return true;
+    };
+    switch (op) {
+      case DR_OP_AND: case DR_OP_OR:
+        if (!emit(ch[0]) || !emit(ch[1])) return false;
+        L.prog.push_back(op == DR_OP_AND ? LEAF_OP_AND : LEAF_OP_OR);
+        L.prog.push_back(0);
+        --depth;
+        return true;
+      case DR_OP_NOT:
+        if (!emit(ch[0])) return false;
+        L.prog.push_back(LEAF_OP_NOT);
+        L.prog.push_back(0);
+        return true;
+      case DR_OP_ISNULL: case DR_OP_ISNOTNULL:
+        if (!is_col(ch[0])) return false;
+        return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, 0, 0, 0, 0});
+      case DR_OP_EQ: case DR_OP_NE: case DR_OP_LT: case DR_OP_LE: case DR_OP_GT: case DR_OP_GE: case DR_OP_NSEQ: {
+        int32_t c, l, fop = op;
+        if (is_col(ch[0]) && is_lit(ch[1])) {
+          c = p.ops[ch[0]].arg; l = p.ops[ch[1]].arg;
+        } else if (is_lit(ch[0]) && is_col(ch[1])) {
+          c = p.ops[ch[1]].arg; l = p.ops[ch[0]].arg;
+          fop = op == DR_OP_LT ? DR_OP_GT : op == DR_OP_GT ? DR_OP_LT : op == DR_OP_LE ? DR_OP_GE
+              : op == DR_OP_GE ? DR_OP_LE : op;
+        } else {
+          return false;
+        }
+        if (!p.lit_null[l] && !kind_ok(c, l)) return false;
+        const bool widen = !p.lit_null[l] && p.col_types[c] == DR_T_FLOAT && p.lit_types[l] == DR_T_DOUBLE;
+        return push_leaf(FilterLeaf{c, fop, slot(l), 0, p.lit_null[l] ? 1 : 0, widen ? 2 : 0});
+      }
+      case DR_OP_STARTSWITH: case DR_OP_ENDSWITH: case DR_OP_CONTAINS: case DR_OP_LIKE: {
+        // check_program: a STRING column and a STRING or NULL literal (LIKE: compiled, compile_patterns)
+        const int32_t l = p.ops[ch[1]].arg;
+        if (p.lit_null[l]) {  // NULL whatever the value; its type field may hold anything
+          L.i64.push_back(0);
+          L.i64hi.push_back(0);
+          L.str.emplace_back();
+          return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, int32_t(L.i64.size() - 1), 0, 1, 0});
+        }
+        return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, slot(l), 0, 0, 0});
+      }
+      case DR_OP_IN: {
+        if (!is_col(ch[0])) return false;
+        const int32_t c = p.ops[ch[0]].arg;
+        const int kind = leaf_kind(p.col_types[c]);
+        const bool str = kind == DR_T_STRING;
+        bool has_null = false, widen = false;
+        std::vector<int64_t> iv;
+        std::vector<std::pair<int64_t, uint64_t>> dv;  // decimals: (high signed, low unsigned)
+        std::vector<std::string> sv;
+        for (size_t q = 1; q < ch.n; ++q)  // a FLOAT column with a DOUBLE element: all in binary64
+          widen |= is_lit(ch[q]) && !p.lit_null[p.ops[ch[q]].arg] && p.col_types[c] == DR_T_FLOAT &&
+                   p.lit_types[p.ops[ch[q]].arg] == DR_T_DOUBLE;
+        for (size_t q = 1; q < ch.n; ++q) {
+          if (!is_lit(ch[q])) return false;
+          const int32_t l = p.ops[ch[q]].arg;
+          if (p.lit_null[l]) { has_null = true; continue; }
+          if (!kind_ok(c, l)) return false;
+          if (str) {
+            sv.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[l],
+                            size_t(p.lit_str_off[l + 1] - p.lit_str_off[l]));
+          } else if (kind == DR_T_DECIMAL) {
+            int64_t lo, hi;
+            literal_words(p, l, &lo, &hi);
+            dv.emplace_back(hi, uint64_t(lo));
+          } else {
+            iv.push_back(fp_word(l, widen));  // FLOAT / DOUBLE: the key, so the set is sorted by key
+          }
+        }
+        if (kind == DR_T_DECIMAL) {  // sorted as 128-bit values
+          std::sort(dv.begin(), dv.end());
+          dv.erase(std::unique(dv.begin(), dv.end()), dv.end());
+          const int32_t first = int32_t(L.i64.size());
+          for (const auto& d : dv) {
+            L.i64.push_back(int64_t(d.second));
+            L.i64hi.push_back(d.first);
+            L.str.emplace_back();
+          }
+          return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(dv.size()), has_null ? 1 : 0, 0});
+        }
+        std::sort(iv.begin(), iv.end());
+        iv.erase(std::unique(iv.begin(), iv.end()), iv.end());
+        std::sort(sv.begin(), sv.end());  // bytewise (std::string compares as unsigned char)
+        sv.erase(std::unique(sv.begin(), sv.end()), sv.end());
+        const int32_t first = int32_t(L.i64.size());
+        const size_t m = str ? sv.size() : iv.size();
+        // an integer set spanning < 2^16 values: a bitmap, one word read per file instead of a
+        // binary search (pad = 1; literals [min, words, bits...])
+        const bool fp = kind == DR_T_FLOAT || kind == DR_T_DOUBLE;  // the bitmap: one-word integer kinds only
+        if (!str && !fp && m >= 8 && uint64_t(iv.back()) - uint64_t(iv.front()) < 65536) {
+          const uint64_t span = uint64_t(iv.back()) - uint64_t(iv.front()) + 1, nw = (span + 63) / 64;
+          std::vector<uint64_t> bits(nw, 0);
+          for (int64_t x : iv) {
+            const uint64_t d = uint64_t(x) - uint64_t(iv.front());
+            bits[d >> 6] |= uint64_t(1) << (d & 63);
+          }
+          L.i64.push_back(iv.front());
+          L.i64.push_back(int64_t(nw));
+          for (uint64_t w : bits) L.i64.push_back(int64_t(w));
+          L.i64hi.resize(L.i64.size(), 0);
+          L.str.resize(L.i64.size());
+          return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, 1});
+        }
+        for (size_t q = 0; q < m; ++q) {
+          L.i64.push_back(str ? 0 : iv[q]);
+          L.i64hi.push_back(0);
+          L.str.push_back(str ? sv[q] : std::string());
+        }
+        return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, widen ? 2 : 0});
+      }
+      default:
+        return false;
+    }
+  };
+  return emit(p.nops - 1) && max_depth <= 32;
+}
+
+}  // namespace dr
