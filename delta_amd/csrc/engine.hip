@@ -611,6 +611,18 @@ struct PagePlan {
   DBuf<uint32_t> s_ba_vals, s_ba_ok, s_ba_count, s_ba_tile_cnt;
   DBuf<uint64_t> s_ba_tile_off, s_ba_kept;
   DBuf<uint32_t> s_ba_link;
+  // DELTA_* pages (k_dl_scan / k_dl_fc_*): page list (encoding 7 first), value tables, block index,
+  // and the expansion arena of the front-coded strings, sized by the plan's first decode (one
+  // read-back of dl_size; later decodes reuse the sizes: they are a function of the staged bytes)
+  std::vector<uint32_t> dl_pages;
+  uint32_t dl_fc = 0, dl_groups = 0, dl_chunks = 0;
+  uint64_t dl_tab = 0, dl_blk = 0;
+  DBuf<uint32_t> d_dl_pages, s_dl_cnt;
+  DBuf<uint64_t> s_dl_tab, s_dl_blk, s_dl_size, d_dl_out, d_dl_sized;
+  DBuf<uint8_t> dl_arena;
+  std::vector<uint64_t> dl_out, dl_sized_bytes;
+  bool dl_sized = false;
+  uint64_t dl_sizings = 0, dl_arena_bytes = 0;
 };
 
 // Host copy of a staged segment's bytes (the host side keeps them: checkpoint footers / page headers
@@ -1057,8 +1069,18 @@ static void plan_pages(StagedData& s, PagePlan& P) {
             d.dict = dict_idx;
             d.row_base = row;
             row += p.num_values;
-            if (d.encoding != 0 && d.encoding != 2 && d.encoding != 8 && !(d.encoding == 3 && l->type == 0))
+            const bool delta = (d.encoding == 5 && (l->type == 1 || l->type == 2)) ||
+                               ((d.encoding == 6 || d.encoding == 7) && l->type == 6);
+            if (d.encoding != 0 && d.encoding != 2 && d.encoding != 8 && !(d.encoding == 3 && l->type == 0) && !delta)
               fail(DR_E_UNSUPPORTED, fmt("encoding %d not supported for %s", d.encoding, P.paths[c].c_str()));
+            if (delta) {
+              d.dl = 1;
+              d.dl_base = P.dl_tab;
+              d.dl_blk_base = P.dl_blk;
+              P.dl_tab += uint64_t(d.num_values) * (d.encoding == 7 ? 2 : 1);
+              P.dl_blk += dl_blk_entries(d.num_values);
+              P.dl_pages.push_back(uint32_t(P.pages.size()));
+            }
           }
           arena += (uint64_t(d.usize) + 16 + 15) & ~uint64_t(15);
           if (d.phys == 6 && (d.kind == PG_DICT || d.encoding == 0)) {  // PLAIN byte arrays
@@ -1185,6 +1207,24 @@ static void plan_pages(StagedData& s, PagePlan& P) {
   P.s_ba_link = DBuf<uint32_t>(s.ctx, P.ba_tiles.size() * 3);
   P.s_ba_ok = DBuf<uint32_t>(s.ctx, P.ba_pages);
   P.s_ba_count = DBuf<uint32_t>(s.ctx, P.ba_pages);
+  if (!P.dl_pages.empty()) {
+    std::stable_partition(P.dl_pages.begin(), P.dl_pages.end(), [&](uint32_t i) { return P.pages[i].encoding == 7; });
+    for (size_t k = 0; k < P.dl_pages.size(); ++k) {
+      PageDesc& d = P.pages[P.dl_pages[k]];
+      d.dl_slot = uint32_t(k);
+      if (d.encoding == 7) {
+        ++P.dl_fc;
+        P.dl_groups = std::max(P.dl_groups, (d.num_values + 63) / 64);
+      }
+    }
+    up(P.d_dl_pages, P.dl_pages);
+    P.s_dl_tab = DBuf<uint64_t>(s.ctx, P.dl_tab);
+    P.s_dl_blk = DBuf<uint64_t>(s.ctx, 2 * P.dl_blk);
+    P.s_dl_cnt = DBuf<uint32_t>(s.ctx, P.dl_pages.size());
+    P.s_dl_size = DBuf<uint64_t>(s.ctx, 2 * P.dl_pages.size());
+    P.d_dl_out = DBuf<uint64_t>(s.ctx, P.dl_pages.size());
+    P.d_dl_sized = DBuf<uint64_t>(s.ctx, P.dl_pages.size());
+  }
   for (PageDesc& d : P.pages) {
     d.src = pqb + d.src;
     d.dst = arb + d.dst;
@@ -1368,6 +1408,43 @@ static void decode_pages(dr_ctx* ctx, PagePlan& P, ParquetArgs& pa, DBuf<uint64_
                      tc[t]);
         ++shown;
       }
+    }
+  }
+  if (!P.dl_pages.empty()) {
+    const uint32_t ndl = uint32_t(P.dl_pages.size());
+    pa.dl_pages = P.d_dl_pages.p;
+    pa.ndl = ndl;
+    pa.dl_tab = P.s_dl_tab.p;
+    pa.dl_blk = P.s_dl_blk.p;
+    pa.dl_cnt = P.s_dl_cnt.p;
+    pa.dl_size = P.s_dl_size.p;
+    launch_dl_scan(pa, stream);
+    if (P.dl_fc) {
+      if (!P.dl_sized) {
+        // the expansion arena, sized once per plan: each front-coded page's expanded bytes (and the
+        // longest value of any) in one read-back; a refused page reports 0 and the decode fails below
+        const std::vector<uint64_t> sz = d2h(P.s_dl_size.p, 2 * uint64_t(ndl), stream);
+        P.dl_out.assign(ndl, 0);
+        P.dl_sized_bytes.assign(ndl, 0);
+        uint64_t at = 0, longest = 0;
+        for (uint32_t k = 0; k < P.dl_fc; ++k) {
+          P.dl_out[k] = at;
+          P.dl_sized_bytes[k] = sz[2 * k];
+          at += (sz[2 * k] + 16 + 15) & ~uint64_t(15);  // 16 bytes of padding, as the page arena's bodies
+          longest = std::max(longest, sz[2 * k + 1]);
+        }
+        P.dl_arena = DBuf<uint8_t>(ctx, at + 64);
+        P.dl_arena_bytes = at;
+        P.dl_chunks = uint32_t((longest + 63) / 64);
+        HIP_OK(hipMemcpyAsync(P.d_dl_out.p, P.dl_out.data(), ndl * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(P.d_dl_sized.p, P.dl_sized_bytes.data(), ndl * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        P.dl_sized = true;
+        ++P.dl_sizings;
+      }
+      pa.dl_out = P.d_dl_out.p;
+      pa.dl_sized = P.d_dl_sized.p;
+      pa.dl_arena = P.dl_arena.p;
+      launch_dl_expand(pa, P.dl_fc, P.dl_groups, P.dl_chunks, stream);
     }
   }
   launch_pq_dict(pa, stream);
@@ -5581,11 +5658,12 @@ int dr_staged_plan(const dr_staged* staged, uint64_t* out, int32_t cap, int32_t*
   for (auto& p : s.parts) ck += p.len;
   for (auto& p : s.hot.pages) { cs += p.csize; us += p.usize; }
   const PagePlan& h = s.hot;
-  const uint64_t v[14] = {s.h_json.size(), ck, s.ck_rows, s.hot.pages.size(), cs, us, s.hot.dict_entries,
+  const uint64_t v[18] = {s.h_json.size(), ck, s.ck_rows, s.hot.pages.size(), cs, us, s.hot.dict_entries,
                           h.snap_in_bytes, h.snap_out_bytes, h.nchunks, h.block_page.size(), h.snap_elements,
-                          h.copy_bytes, s.json_lines};
+                          h.copy_bytes, s.json_lines, h.dl_pages.size(), h.dl_sizings, h.dl_arena_bytes,
+                          0 /* DELTA_* pages decoded serially: there is no such decoder */};
   int32_t k = 0;
-  for (; k < cap && k < 14; ++k) out[k] = v[k];
+  for (; k < cap && k < 18; ++k) out[k] = v[k];
   *n = k;
   return DR_OK;
 }

@@ -8,7 +8,9 @@
 //    remove.deletionTimestamp): RLE/bit-packed definition levels expanded run-by-run by the whole
 //    wave into LDS, value ranks by ballot prefix counts, values from PLAIN (fixed width, or
 //    length-prefixed byte arrays walked through a 1 KiB register window with readlane) or
-//    PLAIN_DICTIONARY/RLE_DICTIONARY indices.
+//    PLAIN_DICTIONARY/RLE_DICTIONARY indices, or from the value table that k_dl_scan (+ k_dl_fc_last /
+//    k_dl_fc_fill) built for a DELTA_BINARY_PACKED / DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY page.
+#include "delta_enc.h"
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -455,6 +457,314 @@ __global__ void __launch_bounds__(BA_T) k_ba_write(ParquetArgs a) {
   }
 }
 
+// ---- DELTA_* pages (encodings 5, 6, 7; the formats: delta_enc.h) ---------------------------------------
+// k_dl_scan, one workgroup per page: thread 0 walks the block headers of each packed sequence through
+// a 4 KiB LDS window of the body (one restage per ~30 blocks, not one dependent global load per block)
+// into the block index; every thread then unpacks its deltas and a workgroup prefix sum over
+// (delta + min delta) gives the values. INT columns: the values are the table. Lengths (encoding 6):
+// a second scan places each string in the body's byte region. Encoding 7: the prefix and suffix
+// lengths give each value's length, its suffix's place in the byte region and -- a third scan -- its
+// place in the expansion arena; the page's expanded bytes and longest value go to dl_size (the host
+// sizes the arena from them once per staged segment). Every rule of the format is checked here,
+// before any byte is addressed through a length: a refused page gets dl_cnt = DL_BAD and PQE_VALUES.
+constexpr int DL_T = 256;
+constexpr uint32_t DL_WIN = 4096;
+
+struct DlWin {  // bytes of the value region: from the LDS window where it holds them
+  const uint8_t* win;
+  uint64_t wbase;
+  uint32_t wn;
+  const uint8_t* b;
+  uint64_t S;
+  __device__ int operator()(uint64_t pos) const {
+    if (pos >= S) return -1;
+    const uint64_t k = pos - wbase;
+    return k < wn ? int(win[k]) : int(b[pos]);
+  }
+};
+
+// inclusive workgroup prefix sum (wrapping); *total: the workgroup's sum
+__device__ __forceinline__ uint64_t dl_scan_incl(uint64_t x, uint64_t* wsum, uint64_t* total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t v = (uint64_t)__shfl_up((unsigned long long)x, o, 64);
+    if (lane >= o) x += v;
+  }
+  if (lane == 63) wsum[wv] = x;
+  __syncthreads();
+  uint64_t before = 0, tot = 0;
+  for (int k = 0; k < DL_T / 64; ++k) {
+    before += k < wv ? wsum[k] : 0;
+    tot += wsum[k];
+  }
+  __syncthreads();
+  *total = tot;
+  return x + before;
+}
+
+__global__ void __launch_bounds__(DL_T) k_dl_scan(ParquetArgs a) {
+  const uint32_t slot = blockIdx.x;
+  const PageDesc pg = a.pages[a.dl_pages[slot]];
+  __shared__ __attribute__((aligned(16))) uint8_t win[DL_WIN];
+  __shared__ uint64_t wsum[DL_T / 64];
+  __shared__ uint64_t s_len[DL_T];
+  __shared__ denc::DbpHeader hdr[2];
+  __shared__ uint64_t s_pos, s_left;
+  __shared__ uint32_t s_nblk, s_bad, s_max;
+  const uint32_t tid = threadIdx.x;
+  const uint8_t *b = nullptr, *e = nullptr;
+  const bool region = ba_region(pg, &b, &e) && b <= e;
+  if (!region) {
+    if (tid == 0) {
+      set_err(a.error, PQE_LEVELS);
+      a.dl_cnt[slot] = DL_BAD;
+      a.dl_size[2 * slot] = a.dl_size[2 * slot + 1] = 0;
+    }
+    return;
+  }
+  const uint64_t S = uint64_t(e - b);
+  const uint64_t boff = uint64_t(b - reinterpret_cast<const uint8_t*>(pg.dst));
+  const int nseq = pg.encoding == 7 ? 2 : 1;
+  const int max_w = pg.encoding == 5 && pg.phys == 2 ? 64 : 32;  // lengths are INT32 sequences
+  uint64_t* tab = a.dl_tab + pg.dl_base;
+  const uint64_t blk_cap = dl_blk_entries(pg.num_values) / 2;  // blocks per sequence
+  uint64_t* blk = a.dl_blk + 2 * pg.dl_blk_base;               // (width bytes' position, min delta)
+  if (tid == 0) {
+    s_pos = 0;
+    s_bad = 0;
+    s_max = 0;
+  }
+  __syncthreads();
+  for (int q = 0; q < nseq; ++q) {
+    if (tid == 0) {
+      uint64_t pos = s_pos;
+      const denc::PtrReader rd{b, S};
+      denc::DbpHeader h;
+      if (!denc::dbp_header(rd, pos, pg.num_values, &h) || denc::dbp_blocks(h) > blk_cap ||
+          (q == 1 && h.count != hdr[0].count)) {
+        s_bad = 1;
+        h.count = 0;
+      }
+      hdr[q] = h;
+      s_pos = pos;
+      s_left = h.count ? h.count - 1 : 0;
+      s_nblk = 0;
+    }
+    __syncthreads();
+    // block index
+    for (;;) {
+      const uint64_t left0 = s_left, wbase = s_pos;
+      if (!left0) break;
+      const uint32_t wn = uint32_t(min(uint64_t(DL_WIN), S - wbase));
+      if (16 * tid + 16 <= wn) {
+        const uint8_t* g = b + wbase + 16 * tid;
+        uint64_t* w8 = reinterpret_cast<uint64_t*>(win + 16 * tid);
+        w8[0] = load_u64(g);
+        w8[1] = load_u64(g + 8);
+      } else {
+        for (uint32_t k = 16 * tid; k < wn && k < 16 * tid + 16; ++k) win[k] = b[wbase + k];
+      }
+      __syncthreads();
+      if (tid == 0) {
+        const DlWin rd{win, wbase, wn, b, S};
+        const denc::DbpHeader h = hdr[q];
+        uint64_t pos = wbase, left = left0;
+        uint32_t nb = s_nblk;
+        do {
+          denc::DbpBlock bk;
+          if (nb >= blk_cap || !denc::dbp_block(rd, pos, S, h, left, max_w, &bk)) {
+            s_bad = 1;
+            left = 0;
+            break;
+          }
+          blk[2 * (q * blk_cap + nb)] = bk.w_pos;
+          blk[2 * (q * blk_cap + nb) + 1] = uint64_t(bk.min_delta);
+          ++nb;
+          pos = bk.next_pos;
+          left -= min(left, uint64_t(h.block));
+        } while (left && pos - wbase + 16 + h.nmb <= wn);
+        s_pos = pos;
+        s_left = left;
+        s_nblk = nb;
+      }
+      __syncthreads();
+    }
+    if (s_bad) break;
+    // unpack + scan
+    const denc::DbpHeader h = hdr[q];
+    uint64_t* T = tab + uint64_t(q) * pg.num_values;
+    uint64_t carry = uint64_t(h.first);
+    if (tid == 0 && h.count) T[0] = uint64_t(max_w == 32 ? denc::dbp_narrow32(h.first) : h.first);
+    const uint64_t nd = h.count ? h.count - 1 : 0;
+    for (uint64_t d0 = 0; d0 < nd; d0 += DL_T) {
+      const uint64_t d = d0 + tid;
+      uint64_t x = 0;
+      if (d < nd) {
+        const uint64_t* be = blk + 2 * (q * blk_cap + d / h.block);
+        x = be[1] + denc::dbp_delta(b, h, be[0], uint32_t(d % h.block));
+      }
+      uint64_t tot;
+      const uint64_t inc = dl_scan_incl(x, wsum, &tot);
+      if (d < nd) {
+        const int64_t v = int64_t(carry + inc);
+        T[d + 1] = uint64_t(max_w == 32 ? denc::dbp_narrow32(v) : v);
+      }
+      carry += tot;
+    }
+    __syncthreads();
+  }
+  const uint32_t count = hdr[0].count;
+  const uint64_t bytes0 = s_pos;         // the byte region follows the last sequence
+  bool bad = false;
+  uint64_t expanded = 0;
+  if (!s_bad && pg.encoding == 6) {
+    const uint64_t R = S - bytes0;
+    uint64_t run = 0;
+    for (uint32_t i0 = 0; i0 < count; i0 += DL_T) {
+      const uint32_t i = i0 + tid;
+      int64_t len = i < count ? int64_t(tab[i]) : 0;
+      if (len < 0) {
+        bad = true;
+        len = 0;
+      }
+      uint64_t tot;
+      const uint64_t off = run + dl_scan_incl(uint64_t(len), wsum, &tot) - uint64_t(len);
+      if (i < count) {
+        if (off + uint64_t(len) > R) bad = true;
+        else tab[i] = ((boff + bytes0 + off) << 32) | uint64_t(len);
+      }
+      run += tot;
+    }
+  } else if (!s_bad && pg.encoding == 7) {
+    const uint64_t R = S - bytes0;
+    uint64_t* T1 = tab + pg.num_values;
+    uint64_t run_s = 0, run_o = 0, prev_len = 0;
+    uint32_t mx = 0;
+    for (uint32_t i0 = 0; i0 < count; i0 += DL_T) {
+      const uint32_t i = i0 + tid;
+      int64_t pf = i < count ? int64_t(tab[i]) : 0, sl = i < count ? int64_t(T1[i]) : 0;
+      if (pf < 0 || sl < 0) {
+        bad = true;
+        pf = sl = 0;
+      }
+      const uint64_t len = uint64_t(pf) + uint64_t(sl);
+      s_len[tid] = len;
+      __syncthreads();
+      // pages are independent (the first prefix is 0); no prefix exceeds the value before it
+      const uint64_t before = tid ? s_len[tid - 1] : prev_len;
+      if (i < count && (i == 0 ? pf != 0 : uint64_t(pf) > before)) bad = true;
+      prev_len = s_len[DL_T - 1];
+      uint64_t tot_s, tot_o;
+      const uint64_t off_s = run_s + dl_scan_incl(uint64_t(sl), wsum, &tot_s) - uint64_t(sl);
+      const uint64_t off_o = run_o + dl_scan_incl(len, wsum, &tot_o) - len;
+      if (i < count) {
+        if (off_s + uint64_t(sl) > R || off_o + len > 0xFFFFFFFFull) {
+          bad = true;
+        } else {
+          T1[i] = ((boff + bytes0 + off_s) << 32) | uint64_t(sl);
+          tab[i] = (off_o << 32) | len;
+          mx = max(mx, uint32_t(len));
+        }
+      }
+      run_s += tot_s;
+      run_o += tot_o;
+    }
+    expanded = run_o;
+    atomicMax(&s_max, mx);
+  }
+  if (bad) atomicOr(&s_bad, 1u);
+  __syncthreads();
+  if (tid == 0) {
+    if (s_bad) set_err(a.error, PQE_VALUES);
+    a.dl_cnt[slot] = s_bad ? DL_BAD : count;
+    a.dl_size[2 * slot] = s_bad ? 0 : expanded;
+    a.dl_size[2 * slot + 1] = s_bad ? 0 : s_max;
+  }
+}
+
+// Front-coding expansion (encoding 7). Value i is the first prefix[i] bytes of value i-1, then its
+// suffix, so byte k of value i is byte k - prefix[j] of the suffix of the greatest j <= i with
+// prefix[j] <= k: the byte columns are independent of each other. A wave owns 64 columns (lane = byte
+// k) and keeps, per lane, where byte k of the current value lies in the page body; walking the values
+// in order, value j moves the lanes with k >= prefix[j] to its suffix and leaves the others alone.
+//  k_dl_fc_last: one wave per (page, 64 columns) walks all values of the page -- a few scalar reads
+//    and one compare-and-select per value, no memory traffic -- and writes the last value of every
+//    full group of 64 values into the arena.
+//  k_dl_fc_fill: one wave per (group, 64 columns) starts from the preceding group's last value (in
+//    the arena) and writes the group's other values, a coalesced byte load and store per value.
+// Work: O(values * columns of the longest value / 64 + bytes out); nothing walks back through the page.
+__device__ __forceinline__ uint32_t dl_rl(uint32_t v, int j) { return uint32_t(__builtin_amdgcn_readlane(int(v), j)); }
+
+__device__ __forceinline__ bool dl_fc_page(const ParquetArgs& a, uint32_t slot, bool report) {
+  if (a.dl_cnt[slot] == DL_BAD) return false;
+  if (a.dl_size[2 * slot] != a.dl_sized[slot]) {  // the arena was sized for other bytes: write nothing
+    if (report) set_err(a.error, PQE_VALUES);
+    return false;
+  }
+  return true;
+}
+
+__global__ void __launch_bounds__(64) k_dl_fc_last(ParquetArgs a) {
+  const uint32_t slot = blockIdx.x;  // pages of encoding 7 come first
+  const int lane = threadIdx.x;
+  if (!dl_fc_page(a, slot, lane == 0 && blockIdx.y == 0)) return;
+  const uint32_t n = a.dl_cnt[slot];
+  const uint64_t maxlen = a.dl_size[2 * slot + 1];
+  const PageDesc pg = a.pages[a.dl_pages[slot]];
+  const uint8_t* body = reinterpret_cast<const uint8_t*>(pg.dst);
+  const uint64_t* T0 = a.dl_tab + pg.dl_base;
+  const uint64_t* T1 = T0 + pg.num_values;
+  uint8_t* out = a.dl_arena + a.dl_out[slot];
+  for (uint64_t c0 = uint64_t(blockIdx.y) * 64; c0 < maxlen; c0 += uint64_t(gridDim.y) * 64) {
+    const uint64_t k = c0 + lane;
+    uint32_t src = 0;  // body offset of byte k of the current value (read only where the value has one)
+    for (uint32_t g0 = 0; g0 + 64 <= n; g0 += 64) {
+      const uint64_t e0 = T0[g0 + lane], e1 = T1[g0 + lane];
+      const uint32_t len_l = uint32_t(e0), sl_l = uint32_t(e1), so_l = uint32_t(e1 >> 32);
+      for (int j = 0; j < 64; ++j) {
+        const uint32_t len = dl_rl(len_l, j);
+        if (len <= c0) continue;  // no byte in these columns; a later value reaching them brings its own
+        const uint32_t sl = dl_rl(sl_l, j), so = dl_rl(so_l, j), pf = len - sl;
+        if (k >= pf) src = so + uint32_t(k - pf);
+      }
+      const uint32_t len63 = dl_rl(len_l, 63), oo = dl_rl(uint32_t(e0 >> 32), 63);
+      if (k < len63) out[uint64_t(oo) + k] = body[src];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64) k_dl_fc_fill(ParquetArgs a, uint32_t groups) {
+  const uint32_t slot = blockIdx.x / groups, g0 = (blockIdx.x % groups) * 64;
+  const int lane = threadIdx.x;
+  if (!dl_fc_page(a, slot, false)) return;
+  const uint32_t n = a.dl_cnt[slot];
+  if (g0 >= n) return;
+  const PageDesc pg = a.pages[a.dl_pages[slot]];
+  const uint8_t* body = reinterpret_cast<const uint8_t*>(pg.dst);
+  const uint64_t* T0 = a.dl_tab + pg.dl_base;
+  const uint64_t* T1 = T0 + pg.num_values;
+  uint8_t* out = a.dl_arena + a.dl_out[slot];
+  const int cnt = int(min(64u, n - g0));
+  const uint64_t e0 = lane < cnt ? T0[g0 + lane] : 0, e1 = lane < cnt ? T1[g0 + lane] : 0;
+  const uint32_t len_l = uint32_t(e0), oo_l = uint32_t(e0 >> 32), sl_l = uint32_t(e1), so_l = uint32_t(e1 >> 32);
+  const uint64_t prev_off = g0 ? T0[g0 - 1] >> 32 : 0;
+  uint32_t gmax = len_l;
+  for (int o = 32; o > 0; o >>= 1) gmax = max(gmax, uint32_t(__shfl_xor(int(gmax), o, 64)));
+  for (uint64_t c0 = uint64_t(blockIdx.y) * 64; c0 < gmax; c0 += uint64_t(gridDim.y) * 64) {
+    const uint64_t k = c0 + lane;
+    // byte k of the preceding group's last value (k_dl_fc_last wrote it); read only where this
+    // group's prefixes reach it
+    const uint8_t* src = out + prev_off + k;
+    for (int j = 0; j < cnt; ++j) {
+      const uint32_t len = dl_rl(len_l, j);
+      if (len <= c0) continue;
+      const uint32_t sl = dl_rl(sl_l, j), so = dl_rl(so_l, j), oo = dl_rl(oo_l, j), pf = len - sl;
+      if (k >= pf) src = body + so + (k - pf);
+      if (k < len && j != 63) out[uint64_t(oo) + k] = *src;
+    }
+  }
+}
+
 // ---- dictionary pages --------------------------------------------------------------------------------
 // Pages whose values are all independent of each other (byte arrays with validated parallel
 // boundaries, fixed-width values) are spread over DICT_SLICES workgroups of 256 lanes each; the
@@ -531,13 +841,15 @@ __global__ void __launch_bounds__(64) k_pq_dict(ParquetArgs a) {
 constexpr uint32_t SEG = 1024;   // levels per segment
 constexpr int PQD_T = 256;
 
-__global__ void __launch_bounds__(PQD_T) k_pq_data(ParquetArgs a) {
-  const uint32_t pi = blockIdx.x;
-  if (pi >= a.npages) return;
+// DL: the pages of DELTA_* encodings (k_pq_data_dl, one workgroup per entry of dl_pages); the other
+// pages go through the DL = false body, which holds none of the delta state (k_pq_data keeps the
+// registers and the occupancy it had before delta pages existed).
+template <bool DL>
+__device__ __forceinline__ void pq_data_body(const ParquetArgs& a, uint32_t pi) {
   // the descriptor copied once (read through a reference, each field was re-loaded after every
   // store the compiler could not prove it does not alias: serial loads inside the loops)
   const PageDesc pg = a.pages[pi];
-  if (pg.kind == PG_DICT) return;
+  if (pg.kind == PG_DICT || (pg.dl != 0) != DL) return;
   __shared__ uint8_t defs[SEG];
   __shared__ uint8_t reps[SEG];
   __shared__ uint32_t idxs[SEG];
@@ -584,9 +896,20 @@ __global__ void __launch_bounds__(PQD_T) k_pq_data(ParquetArgs a) {
     ir.init(p + 1, end, w);
   } else if (rle_bool) {
     ir.init(p + 4, end, 1);
-  } else if (pg.encoding != 0) {
+  } else if (pg.encoding != 0 && !DL) {
     if (tid == 0) set_err(a.error, PQE_ENCODING);
     return;
+  }
+  // DELTA_* pages: value rank -> the table k_dl_scan built
+  constexpr bool dl = DL;
+  uint32_t dl_n = 0;
+  const uint64_t* dl_tab = nullptr;
+  const uint8_t* dl_bytes = nullptr;
+  if constexpr (DL) {
+    dl_n = a.dl_cnt[pg.dl_slot];
+    if (dl_n == DL_BAD) return;  // refused by k_dl_scan (the error is set)
+    dl_tab = a.dl_tab + pg.dl_base;
+    dl_bytes = pg.encoding == 7 ? a.dl_arena + a.dl_out[pg.dl_slot] : reinterpret_cast<const uint8_t*>(pg.dst);
   }
   const uint32_t dict_base = dict ? a.pages[pg.dict].dict_base : 0;
   const uint32_t dict_n = dict ? a.pages[pg.dict].num_values : 0;
@@ -596,7 +919,7 @@ __global__ void __launch_bounds__(PQD_T) k_pq_data(ParquetArgs a) {
   const uint32_t* ba_vals = a.ba_vals + pg.ba_base;
   const uint32_t ba_n = ba_fast ? a.ba_count[pg.ba_slot] : 0;
   const uint8_t* body = reinterpret_cast<const uint8_t*>(pg.dst);
-  const bool walk = pg.phys == 6 && !dict && !ba_fast;
+  const bool walk = pg.phys == 6 && !dict && !ba_fast && !dl;
   if (walk && wv == 0) wk.init(p, end, lane);
   if (tid == 0) s_bad = 0;
   uint64_t vbase = 0;  // values consumed before this segment (PLAIN fixed / boolean)
@@ -634,6 +957,8 @@ __global__ void __launch_bounds__(PQD_T) k_pq_data(ParquetArgs a) {
     if (dict || rle_bool) {
       ir.expand(vlen, nv, tid, PQD_T);  // dictionary indices / booleans (reuse vlen as scratch)
       if (ir.bad) { if (tid == 0) set_err(a.error, dict ? PQE_DICT : PQE_VALUES); return; }
+    } else if (dl) {
+      if (vbase + nv > dl_n) { if (tid == 0) set_err(a.error, PQE_VALUES); return; }
     } else if (ba_fast) {
       if (vbase + nv > ba_n) { if (tid == 0) set_err(a.error, PQE_VALUES); return; }
     } else if (walk) {
@@ -674,6 +999,14 @@ __global__ void __launch_bounds__(PQD_T) k_pq_data(ParquetArgs a) {
         }
       } else if (rle_bool) {
         col.ival[row] = vlen[k] & 1;
+      } else if (dl) {
+        const uint64_t ent = dl_tab[vbase + k];
+        if (pg.phys == 6) {
+          col.sptr[row] = reinterpret_cast<uint64_t>(dl_bytes + (ent >> 32));
+          col.slen[row] = uint32_t(ent);
+        } else {
+          col.ival[row] = int64_t(ent);
+        }
       } else if (ba_fast) {
         const uint32_t off = ba_vals[vbase + k];
         col.sptr[row] = reinterpret_cast<uint64_t>(body + off + 4);
@@ -693,6 +1026,15 @@ __global__ void __launch_bounds__(PQD_T) k_pq_data(ParquetArgs a) {
     vbase += nv;
     __syncthreads();
   }
+  // a delta page holds exactly its defined levels' values
+  if (dl && vbase != dl_n && tid == 0) set_err(a.error, PQE_VALUES);
+}
+
+__global__ void __launch_bounds__(PQD_T) k_pq_data(ParquetArgs a) {
+  if (blockIdx.x < a.npages) pq_data_body<false>(a, blockIdx.x);
+}
+__global__ void __launch_bounds__(PQD_T) k_pq_data_dl(ParquetArgs a) {
+  if (blockIdx.x < a.ndl) pq_data_body<true>(a, a.dl_pages[blockIdx.x]);
 }
 
 // Checkpoint row -> action. unwrap priority add > remove (D/actions/actions.scala:523-541);
@@ -790,6 +1132,15 @@ void launch_ba_bounds(const ParquetArgs& a, hipStream_t st, ScanScratch scan_scr
   launch_scan_u32(a.ba_tile_cnt, a.ba_tile_off, a.nba_tiles, scan_scratch, st);
   DR_LAUNCH(dev::k_ba_write, dim3(a.nba_tiles), dim3(dev::BA_T), 0, st, a);
 }
+void launch_dl_scan(const ParquetArgs& a, hipStream_t st) {
+  if (a.ndl) DR_LAUNCH(dev::k_dl_scan, dim3(a.ndl), dim3(dev::DL_T), 0, st, a);
+}
+void launch_dl_expand(const ParquetArgs& a, uint32_t nfc, uint32_t groups, uint32_t chunks, hipStream_t st) {
+  if (!nfc || !groups || !chunks) return;
+  const uint32_t y = chunks < 256u ? chunks : 256u;
+  DR_LAUNCH(dev::k_dl_fc_last, dim3(nfc, y), dim3(64), 0, st, a);
+  DR_LAUNCH(dev::k_dl_fc_fill, dim3(nfc * groups, y), dim3(64), 0, st, a, groups);
+}
 void launch_pq_dict(const ParquetArgs& a, hipStream_t st) {
   if (!a.npages) return;
   DR_LAUNCH(dev::k_pq_dict_fast, dim3(a.npages, dev::DICT_SLICES), dim3(256), 0, st, a);
@@ -797,6 +1148,7 @@ void launch_pq_dict(const ParquetArgs& a, hipStream_t st) {
 }
 void launch_pq_data(const ParquetArgs& a, hipStream_t st) {
   if (a.npages) DR_LAUNCH(dev::k_pq_data, dim3(a.npages), dim3(dev::PQD_T), 0, st, a);
+  if (a.ndl) DR_LAUNCH(dev::k_pq_data_dl, dim3(a.ndl), dim3(dev::PQD_T), 0, st, a);
 }
 void launch_ckpt_assemble(const CkptAssembleArgs& a, hipStream_t st) {
   if (a.nrows)

@@ -131,6 +131,12 @@ struct PageDesc {
   uint32_t ba_slot;      // index into ba_ok / ba_count
   uint64_t ba_base;      // first u32 slot of this page's value offsets
   uint64_t hit_base;     // index of this page's first 4 KiB boundary tile (ParquetArgs::ba_tiles)
+  // DELTA_BINARY_PACKED / DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY data pages (encoding 5 / 6 / 7)
+  int32_t dl;            // 1 if this page's values are delta-encoded
+  uint32_t dl_slot;      // index into dl_pages / dl_cnt / dl_size / dl_out
+  uint64_t dl_base;      // first entry of this page's value table (dl_tab): num_values entries, twice
+                         // that for encoding 7
+  uint64_t dl_blk_base;  // first entry of this page's block index (dl_blk)
 };
 
 // Decoded column: one entry per checkpoint row (flat leaf) or per level entry (repeated leaf).
@@ -161,7 +167,27 @@ struct ParquetArgs {
   uint64_t* ba_kept;     // [nba_tiles * 256] kept-candidate masks (64 positions per thread)
   uint32_t* ba_link;     // [nba_tiles * 3] the tile's first kept offset, its last kept's successor
                          // (0xFFFFFFFF: none) and whether its chain broke inside it
+  // DELTA_* pages (k_dl_scan, k_dl_fc_last, k_dl_fc_fill)
+  const uint32_t* dl_pages;  // [ndl] page index of each delta page
+  uint32_t ndl;
+  uint64_t* dl_tab;      // value tables: an INT value, or (byte offset << 32 | length) of a string --
+                         // the offset from the page body (encoding 6) or from the page's first byte in
+                         // the expansion arena (encoding 7; its second table: offset from the body and
+                         // length of each suffix)
+  uint64_t* dl_blk;      // block index: (position of the width bytes, min delta) per block
+  uint32_t* dl_cnt;      // [ndl] values of the page (DL_BAD: the page was refused)
+  uint64_t* dl_size;     // [2 ndl] encoding 7: expanded bytes of the page, and its longest value
+  const uint64_t* dl_out;   // [ndl] encoding 7: the page's first byte in the expansion arena
+  const uint64_t* dl_sized; // [ndl] encoding 7: the expanded bytes the arena was sized for
+  uint8_t* dl_arena;
 };
+constexpr uint32_t DL_BAD = 0xFFFFFFFFu;
+// block-index entries a page of n levels needs (blocks hold at least 128 values; two sequences)
+DR_HD inline uint64_t dl_blk_entries(uint32_t num_values) { return 2 * (uint64_t(num_values) / 128 + 2); }
+void launch_dl_scan(const ParquetArgs& a, hipStream_t st);
+// nfc: pages of encoding 7 come first in dl_pages; groups: the most 64-value groups of one of them;
+// chunks: 64-byte columns of the longest value
+void launch_dl_expand(const ParquetArgs& a, uint32_t nfc, uint32_t groups, uint32_t chunks, hipStream_t st);
 uint32_t ba_tile_bytes();
 void launch_ba_bounds(const ParquetArgs& a, hipStream_t st, ScanScratch scan_scratch);
 

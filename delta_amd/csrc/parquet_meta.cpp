@@ -5,6 +5,7 @@
 #include <functional>
 
 #include "common.h"
+#include "delta_enc.h"
 #include "snappy_host.h"
 
 namespace dr {
@@ -373,6 +374,70 @@ void plain_values(const uint8_t* p, const uint8_t* end, int type, int64_t n, Hos
   }
 }
 
+// ---- DELTA_* values (delta_enc.h: the rules the device kernels run too) ------------------------
+// One packed sequence at `pos` of [b, b + n): exactly `want` values appended to out.
+void dbp_sequence(const uint8_t* b, uint64_t n, uint64_t& pos, bool int32, int64_t want, std::vector<int64_t>& out,
+                  const std::string& name) {
+  const denc::PtrReader rd{b, n};
+  denc::DbpHeader h;
+  if (!denc::dbp_header(rd, pos, uint64_t(want), &h))
+    fail(DR_E_PARQUET, fmt("malformed DELTA_BINARY_PACKED header (column %s)", name.c_str()));
+  if (int64_t(h.count) != want)
+    fail(DR_E_PARQUET, fmt("DELTA_BINARY_PACKED holds %u values, the page defines %lld (column %s)", h.count,
+                           (long long)want, name.c_str()));
+  if (!h.count) return;
+  int64_t v = int32 ? denc::dbp_narrow32(h.first) : h.first;
+  out.push_back(v);
+  uint64_t left = uint64_t(h.count) - 1;
+  while (left) {
+    denc::DbpBlock blk;
+    if (!denc::dbp_block(rd, pos, n, h, left, int32 ? 32 : 64, &blk))
+      fail(DR_E_PARQUET, fmt("malformed DELTA_BINARY_PACKED block (column %s)", name.c_str()));
+    const uint64_t here = std::min<uint64_t>(left, h.block);
+    for (uint32_t r = 0; r < here; ++r) {
+      v = denc::dbp_step(v, blk.min_delta, denc::dbp_delta(b, h, blk.w_pos, r));
+      if (int32) v = denc::dbp_narrow32(v);
+      out.push_back(v);
+    }
+    left -= here;
+    pos = blk.next_pos;
+  }
+}
+
+// `n` values of a DELTA_BINARY_PACKED / DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY page body.
+void delta_values(const uint8_t* p, const uint8_t* end, int enc, int type, int64_t n, HostColumn& col,
+                  const std::string& name) {
+  const uint64_t len = uint64_t(end - p);
+  uint64_t pos = 0;
+  if (enc == DELTA_BINARY_PACKED) {
+    if (type != INT32 && type != INT64)
+      fail(DR_E_UNSUPPORTED, fmt("encoding %d not supported (column %s)", enc, name.c_str()));
+    dbp_sequence(p, len, pos, type == INT32, n, col.ivals, name);
+    return;
+  }
+  if (type != BYTE_ARRAY) fail(DR_E_UNSUPPORTED, fmt("encoding %d not supported (column %s)", enc, name.c_str()));
+  std::vector<int64_t> prefix, lens;
+  if (enc == DELTA_BYTE_ARRAY) dbp_sequence(p, len, pos, true, n, prefix, name);
+  dbp_sequence(p, len, pos, true, n, lens, name);
+  std::string prev;
+  for (int64_t i = 0; i < n; ++i) {
+    if (lens[size_t(i)] < 0 || uint64_t(lens[size_t(i)]) > len - pos)
+      fail(DR_E_PARQUET, fmt("delta byte array length out of range (column %s)", name.c_str()));
+    const size_t l = size_t(lens[size_t(i)]);
+    if (enc == DELTA_BYTE_ARRAY) {
+      const int64_t pf = prefix[size_t(i)];
+      if (pf < 0 || uint64_t(pf) > prev.size() || (i == 0 && pf != 0))
+        fail(DR_E_PARQUET, fmt("delta byte array prefix out of range (column %s)", name.c_str()));
+      prev.resize(size_t(pf));
+      prev.append(reinterpret_cast<const char*>(p + pos), l);
+      col.svals.push_back(prev);
+    } else {
+      col.svals.emplace_back(reinterpret_cast<const char*>(p + pos), l);
+    }
+    pos += l;
+  }
+}
+
 }  // namespace
 
 HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChunk& cc, const Leaf& leaf) {
@@ -393,7 +458,7 @@ HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChu
       if (!snappy_decompress(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)))
         fail(DR_E_PARQUET, fmt("corrupt snappy page in %s", cc.path.c_str()));
-    } else {
+    } else if (pg.uncompressed_size > lv) {
       memcpy(buf.data() + lv, body + lv, size_t(pg.uncompressed_size - lv));
     }
     const uint8_t* p = buf.data();
@@ -454,6 +519,9 @@ HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChu
       std::vector<uint32_t> v;
       rle_decode(p, end, 1, nonnull, v);
       for (uint32_t b : v) col.ivals.push_back(b);
+    } else if (pg.encoding == DELTA_BINARY_PACKED || pg.encoding == DELTA_LENGTH_BYTE_ARRAY ||
+               pg.encoding == DELTA_BYTE_ARRAY) {
+      delta_values(p, end, pg.encoding, leaf.type, nonnull, col, cc.path);
     } else {
       fail(DR_E_UNSUPPORTED, fmt("encoding %d not supported (column %s)", pg.encoding, cc.path.c_str()));
     }
@@ -593,7 +661,7 @@ std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const Colum
       if (!snappy_decompress(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)))
         fail(DR_E_PARQUET, fmt("corrupt snappy page in %s", cc.path.c_str()));
-    } else {
+    } else if (pg.uncompressed_size > lv) {
       memcpy(buf.data() + lv, body + lv, size_t(pg.uncompressed_size - lv));
     }
     const uint8_t* p = buf.data();
@@ -625,6 +693,7 @@ std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const Colum
     if (rep.empty()) rep.push_back({0, pg.num_values});
     if (def.empty()) def.push_back({uint32_t(leaf.max_def), pg.num_values});
     ValueStream vs;
+    HostColumn dl;  // a DELTA_* page's values
     vs.p = p; vs.end = end; vs.type = leaf.type;
     if (pg.encoding == PLAIN_DICTIONARY || pg.encoding == RLE_DICTIONARY) {
       if (!have_dict) fail(DR_E_PARQUET, "dictionary-encoded page without a dictionary");
@@ -648,6 +717,15 @@ std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const Colum
       vs.type = INT64;
       vs.idx.resize(bits.size());
       for (size_t i = 0; i < bits.size(); ++i) vs.idx[i] = uint32_t(i);
+    } else if (pg.encoding == DELTA_BINARY_PACKED || pg.encoding == DELTA_LENGTH_BYTE_ARRAY ||
+               pg.encoding == DELTA_BYTE_ARRAY) {
+      int64_t nonnull = 0;
+      for (auto& r : def) if (int(r.v) == leaf.max_def) nonnull += r.n;
+      delta_values(p, end, pg.encoding, leaf.type, nonnull, dl, cc.path);
+      vs.dict = true;  // the page's values, read through an identity index
+      vs.dictv = &dl;
+      vs.idx.resize(size_t(nonnull));
+      for (size_t i = 0; i < vs.idx.size(); ++i) vs.idx[i] = uint32_t(i);
     } else if (pg.encoding != PLAIN) {
       fail(DR_E_UNSUPPORTED, fmt("encoding %d not supported (column %s)", pg.encoding, cc.path.c_str()));
     }

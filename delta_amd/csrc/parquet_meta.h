@@ -14,7 +14,8 @@ enum PhysType { BOOLEAN = 0, INT32 = 1, INT64 = 2, INT96 = 3, FLOAT = 4, DOUBLE 
                 FIXED_LEN_BYTE_ARRAY = 7 };
 enum Repetition { REQUIRED = 0, OPTIONAL = 1, REPEATED = 2 };
 enum Codec { UNCOMPRESSED = 0, SNAPPY = 1 };
-enum Encoding { PLAIN = 0, PLAIN_DICTIONARY = 2, RLE = 3, BIT_PACKED = 4, RLE_DICTIONARY = 8 };
+enum Encoding { PLAIN = 0, PLAIN_DICTIONARY = 2, RLE = 3, BIT_PACKED = 4, DELTA_BINARY_PACKED = 5,
+                DELTA_LENGTH_BYTE_ARRAY = 6, DELTA_BYTE_ARRAY = 7, RLE_DICTIONARY = 8 };
 enum PageType { DATA_PAGE = 0, INDEX_PAGE = 1, DICTIONARY_PAGE = 2, DATA_PAGE_V2 = 3 };
 
 struct SchemaElement {

@@ -242,12 +242,13 @@ class Staged:
         return j.value, c.value
 
     def plan(self) -> Dict[str, int]:
-        out = (C.c_uint64 * 16)()
+        out = (C.c_uint64 * 32)()
         n = C.c_int32()
-        self.eng.check(self.eng.lib.dr_staged_plan(self.h, out, 16, C.byref(n)))
+        self.eng.check(self.eng.lib.dr_staged_plan(self.h, out, 32, C.byref(n)))
         names = ["json_bytes", "checkpoint_bytes", "checkpoint_rows", "pages", "pages_compressed_bytes",
                  "pages_decompressed_bytes", "dict_entries", "snappy_in_bytes", "snappy_out_bytes",
-                 "snappy_chunks", "snappy_blocks", "snappy_elements", "copy_bytes", "json_lines"]
+                 "snappy_chunks", "snappy_blocks", "snappy_elements", "copy_bytes", "json_lines",
+                 "delta_pages", "delta_sizing_passes", "delta_arena_bytes", "delta_pages_serial"]
         return {names[i]: int(out[i]) for i in range(n.value)}
 
     def replay(self, min_file_retention_timestamp: int, validate: bool = True, reducer: str = "lds") -> "State":

@@ -229,9 +229,11 @@ def delta_name(v: int) -> str:
 def write_checkpoint(path: str, pool: FilePool, add_ids: np.ndarray, ncols: int, version: int,
                      with_parsed: bool = False, row_group_size: int = 1 << 20,
                      data_page_size: int = 1 << 20, compression: str = "snappy",
-                     data_page_version: str = "1.0", use_dictionary: bool = True, head: bool = True) -> int:
+                     data_page_version: str = "1.0", use_dictionary: bool = True, head: bool = True,
+                     column_encoding=None) -> int:
     """Rows: protocol, metaData (unless `head` is false: later parts of a multi-part checkpoint),
-    then one `add` per id. Returns the row count."""
+    then one `add` per id. Returns the row count. `column_encoding` ({leaf name: encoding}, e.g.
+    {"add.path": "DELTA_BYTE_ARRAY"}) goes to pyarrow, which wants use_dictionary=False with it."""
     pa, pc = _pa()
     import pyarrow.parquet as pq
 
@@ -313,13 +315,14 @@ def write_checkpoint(path: str, pool: FilePool, add_ids: np.ndarray, ncols: int,
                                  names=["txn", "add", "remove", "metaData", "protocol"])
     pq.write_table(table, path, compression=compression, use_dictionary=use_dictionary, version="1.0",
                    data_page_version=data_page_version, row_group_size=row_group_size,
-                   data_page_size=data_page_size, write_statistics=False)
+                   data_page_size=data_page_size, write_statistics=False, column_encoding=column_encoding)
     return nrows
 
 
 def write_checkpoint_records(path: str, protocol: dict, metadata: dict, adds: list, removes: list = (),
                              txns: list = (), row_group_size: int = 1 << 20, use_dictionary: bool = True,
-                             data_page_version: str = "1.0", data_page_size: int = 1 << 20) -> int:
+                             data_page_version: str = "1.0", data_page_size: int = 1 << 20,
+                             column_encoding=None, compression: str = "snappy") -> int:
     """Checkpoint with the reference's column layout from explicit action records (edge-case
     corpora: any partitionValues / tags maps, nulls). Rows: protocol, metaData, txns, adds, removes
     (protocol / metadata None: no such row, as in DeltaLogSuite's checkpoints missing an action)."""
@@ -370,9 +373,9 @@ def write_checkpoint_records(path: str, protocol: dict, metadata: dict, adds: li
                       ("protocol", prot_type)):
         cols[name] = pa.array([r.get(name) for r in rows], typ)
     table = pa.Table.from_arrays(list(cols.values()), names=list(cols))
-    pq.write_table(table, path, compression="snappy", use_dictionary=use_dictionary, version="1.0",
+    pq.write_table(table, path, compression=compression, use_dictionary=use_dictionary, version="1.0",
                    data_page_version=data_page_version, row_group_size=row_group_size,
-                   data_page_size=data_page_size, write_statistics=False)
+                   data_page_size=data_page_size, write_statistics=False, column_encoding=column_encoding)
     return len(rows)
 
 
@@ -422,7 +425,7 @@ def _pick_live(rng, state, next_id, k):
 def build_table(table_dir: str, spec: ChurnSpec, seed: int, checkpoint_with_parsed=False,
                 data_page_size: int = 1 << 20, keep_ids: bool = True, compression: str = "snappy",
                 data_page_version: str = "1.0", row_group_size: int = 1 << 20,
-                use_dictionary: bool = True, workers: int = 1) -> Expected:
+                use_dictionary: bool = True, workers: int = 1, column_encoding=None) -> Expected:
     rng = np.random.default_rng(seed)
     log = os.path.join(table_dir, "_delta_log")
     os.makedirs(log, exist_ok=True)
@@ -445,6 +448,8 @@ def build_table(table_dir: str, spec: ChurnSpec, seed: int, checkpoint_with_pars
         kw = dict(ncols=spec.ncols, version=version, with_parsed=checkpoint_with_parsed,
                   data_page_size=data_page_size, compression=compression, data_page_version=data_page_version,
                   row_group_size=row_group_size, use_dictionary=use_dictionary)
+        if column_encoding is not None:
+            kw["column_encoding"] = column_encoding
         names = [os.path.join(log, "%020d.checkpoint.parquet" % version if parts == 1 else
                               "%020d.checkpoint.%010d.%010d.parquet" % (version, k + 1, parts))
                  for k in range(parts)]

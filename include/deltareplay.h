@@ -195,7 +195,13 @@ int dr_log_segment(dr_ctx* ctx, const char* log_path, int64_t version_to_load,
 
 /* ---- staging (host -> HBM) ----------------------------------------------------------------
  * Copies the segment's file bytes into HBM and plans the Parquet page decode (footer + page
- * headers, host). The staged input is reusable across dr_replay_staged calls. */
+ * headers, host). The staged input is reusable across dr_replay_staged calls.
+ * Checkpoint parts: DATA_PAGE and DATA_PAGE_V2 pages, UNCOMPRESSED or SNAPPY, with the value encodings
+ * PLAIN, PLAIN_DICTIONARY / RLE_DICTIONARY, RLE (booleans), DELTA_BINARY_PACKED (INT32, INT64),
+ * DELTA_LENGTH_BYTE_ARRAY and DELTA_BYTE_ARRAY (byte arrays). Any other pair of encoding and physical
+ * type (BYTE_STREAM_SPLIT, FIXED_LEN_BYTE_ARRAY, ...) fails with DR_E_UNSUPPORTED at staging; a
+ * malformed page fails the replay with DR_E_PARQUET. A DELTA_BYTE_ARRAY page must stand alone (its
+ * first prefix length is 0). */
 int dr_stage(dr_ctx* ctx, const dr_file* files, int32_t nfiles, dr_staged** out);
 /* dr_stage with each file's name (a path or file: URI; "" = unnamed, as the reference's cached
  * snapshots): every named file must sit directly in `log_path` -- the check Snapshot.stateReconstruction
@@ -214,7 +220,10 @@ int dr_staged_bytes(const dr_staged* staged, uint64_t* json_bytes, uint64_t* che
  * [2] checkpoint rows, [3] planned pages, [4] their compressed bytes, [5] their decompressed bytes,
  * [6] dictionary entries, [7] SNAPPY input bytes, [8] SNAPPY output bytes, [9] SNAPPY 256-byte
  * speculation chunks, [10] SNAPPY 64 KiB output blocks, [11] SNAPPY elements (0 until a replay with
- * timing on has counted them), [12] bytes of uncompressed pages copied, [13] JSON lines (newline-terminated). *n receives the number of
+ * timing on has counted them), [12] bytes of uncompressed pages copied, [13] JSON lines (newline-terminated),
+ * [14] DELTA_* pages of the hot columns, [15] sizing passes run for their expansion arena (one read-back
+ * each: 0 before the first replay or without DELTA_BYTE_ARRAY pages, then 1), [16] bytes of that arena,
+ * [17] DELTA_* pages decoded serially (always 0: there is no serial decoder). *n receives the number of
  * figures written (<= cap). */
 int dr_staged_plan(const dr_staged* staged, uint64_t* out, int32_t cap, int32_t* n);
 
