@@ -25,9 +25,11 @@
 #if defined(__HIPCC__)
 #define JL_HD __host__ __device__ __forceinline__
 #define JL_UNROLL _Pragma("unroll")
+#define JL_NOUNROLL _Pragma("nounroll")
 #else
 #define JL_HD inline
 #define JL_UNROLL
+#define JL_NOUNROLL
 #endif
 
 namespace dr {
@@ -837,6 +839,143 @@ JL_HD void dfa_finish(const Tokenizer& tz, const Dfa<General>& d, LineOut& out) 
     out.size = ad ? d.fadd.size : d.frm.size;
     out.delts = ad ? d.fadd.delts : d.frm.delts;
   }
+}
+
+// ---- writer-shaped add / remove lines without the DFA -------------------------------------------------
+// Nearly every line of a commit is an add or a remove that a Delta writer serialised (Jackson over
+// AddFile / RemoveFile): members in declaration order, no whitespace, no escapes in member names, one
+// nested object (partitionValues). For such a line the DFA's answer follows from the token classes,
+// a few key compares and the scalars, so match_writer_line checks the line's whole token column
+// against a shape and fills the LineOut without stepping the machine. It accepts only what it can
+// decide exactly as dfa_token + dfa_finish would; anything else it declines (the caller then runs
+// the DFA over the same tokens), and it never reports an error row.
+//
+// A shape is data: the members of the file object in order, each a key length, what file_key_w must
+// say of the key, and the kind of value. A member marked `opt` may be the point where the object
+// ends instead (everything from it on is absent); after the last member the object must end.
+//   add:    path, partitionValues, size, modificationTime, dataChange [, stats]
+//   remove: path, deletionTimestamp, dataChange [, extendedFileMetadata, partitionValues, size]
+// (`tags` is declined: its key has the length of `path` / `size`, and writers rarely set it.)
+// A key is accepted when its length is the member's and file_key_w classifies it as the member's
+// role: for the members the DFA ignores (FK_OTHER) that is the whole of what the DFA asks of them,
+// since only a key of 4 or 17 bytes can be path / size / deletionTimestamp.
+enum : uint8_t { WV_STRING = 0, WV_SCALAR = 1, WV_PVALS = 2 };
+struct WMember {
+  uint8_t klen, fk, val, opt;
+};
+constexpr WMember W_ADD[] = {{4, FK_PATH, WV_STRING, 0},   {15, FK_OTHER, WV_PVALS, 0},  {4, FK_SIZE, WV_SCALAR, 0},
+                             {16, FK_OTHER, WV_SCALAR, 0}, {10, FK_OTHER, WV_SCALAR, 0}, {5, FK_OTHER, WV_STRING, 1}};
+constexpr WMember W_REMOVE[] = {{4, FK_PATH, WV_STRING, 0},   {17, FK_DELTS, WV_SCALAR, 0}, {10, FK_OTHER, WV_SCALAR, 0},
+                                {20, FK_OTHER, WV_SCALAR, 1}, {15, FK_OTHER, WV_PVALS, 0},  {4, FK_SIZE, WV_SCALAR, 0}};
+// A shape as one word, ten bits a member (klen:5 fk:2 val:2 opt:1), first member lowest; klen is
+// never 0, so the word runs out exactly after the last member. The walk below is one loop over it.
+constexpr uint32_t W_BITS = 10;
+template <int N>
+constexpr uint64_t wshape(const WMember (&m)[N]) {
+  static_assert(N * W_BITS <= 64, "a shape is one 64-bit word");
+  uint64_t s = 0;
+  for (int i = N - 1; i >= 0; --i)
+    s = (s << W_BITS) | uint64_t(m[i].klen | (m[i].fk << 5) | (m[i].val << 7) | (m[i].opt << 9));
+  return s;
+}
+constexpr uint64_t W_ADD_SHAPE = wshape(W_ADD), W_REMOVE_SHAPE = wshape(W_REMOVE);
+
+// `tok[t * stride]`, t < nt, are the line's tokens (all of them: the tokenizer has finished), `tz`
+// its tokenizer. Returns false (declined, `out` unspecified) or true with `out` what dfa_token over
+// the same tokens and dfa_finish would give; then out.kind is K_ADD or K_REMOVE.
+JL_HD bool match_writer_line(const uint8_t* p, uint32_t n, const uint32_t* tok, uint32_t stride, uint32_t nt,
+                             const Tokenizer& tz, LineOut& out) {
+  (void)n;
+  if (tz.status != ST_OK) return false;
+  uint32_t t = 0;
+  auto next = [&]() -> uint32_t { return t < nt ? tok[(t++) * stride] : TOK_NONE; };  // TOK_NONE matches nothing
+  constexpr uint32_t CF = 0x3Fu;  // class and folded punctuation
+  if ((next() & CF) != T_OBJ_OPEN) return false;
+  const uint32_t ak = next();
+  if ((ak & CF) != (T_STRING | TF_COLON)) return false;
+  const uint8_t kind = action_key_w(p + tok_off(ak) + 1, tok_aux(ak));
+  if (kind != K_ADD && kind != K_REMOVE) return false;
+  if ((next() & CF) != T_OBJ_OPEN) return false;
+  uint32_t checked = 0;  // scalar bytes validated here (dfa_finish's sc_checked)
+  uint32_t path_off = 0, path_len = 0;
+  uint8_t flags = F_PATH_NULL;
+  int64_t size = 0, delts = 0;
+  bool comma = true;  // a ',' (or the object's '{') stands before the next member
+JL_NOUNROLL
+  for (uint64_t shape = kind == K_ADD ? W_ADD_SHAPE : W_REMOVE_SHAPE; shape; shape >>= W_BITS) {
+    const uint32_t m = uint32_t(shape) & ((1u << W_BITS) - 1u);
+    const uint32_t klen = m & 31u, fk = (m >> 5) & 3u, val = (m >> 7) & 3u;
+    if (!comma) {
+      if (!(m >> 9)) return false;  // the object ends where the shape has a mandatory member
+      break;
+    }
+    const uint32_t k = next();
+    if ((k & CF) != (T_STRING | TF_COLON) || tok_aux(k) != klen) return false;
+    if (file_key_w(p + tok_off(k) + 1, klen) != fk) return false;
+    uint32_t v = next();  // the member's value; after WV_PVALS, the '}' that closes it
+    const uint32_t cls = tok_cls(v);
+    if (val == WV_STRING) {
+      if (cls != T_STRING && cls != T_STRING_ESC) return false;
+      if (fk == FK_PATH) {
+        path_off = tok_off(v) + 1;
+        path_len = tok_aux(v);
+        flags = cls == T_STRING_ESC ? F_PATH_ESCAPED : 0;
+      }
+    } else if (val == WV_SCALAR) {
+      if (cls != T_SCALAR) return false;
+      int64_t x = 0;
+      const uint8_t sc = scalar_fast(p + tok_off(v), tok_aux(v), &x);
+      if (sc == SC_BAD) return false;
+      checked += tok_aux(v);
+      if (fk != FK_OTHER) {  // LongType: an integer in range, or null (absent)
+        if (sc != SC_INT && sc != SC_NULL) return false;
+        if (fk == FK_SIZE) size = x;
+        else {
+          delts = x;
+          if (sc == SC_INT) flags |= F_HAS_DELTS;
+        }
+      }
+    } else {  // partitionValues: { ("key": "value" | null ,)* }
+      if ((v & CF) != T_OBJ_OPEN) return false;
+      bool need_key = false;
+      for (;;) {
+        v = next();
+        if ((v & CF) != (T_STRING | TF_COLON)) break;
+        const uint32_t pv = next();
+        const uint32_t pc = tok_cls(pv), pf = pv & TF_MASK;
+        if (pc == T_SCALAR) {
+          uint32_t w[5];
+          load20(p + tok_off(pv), 4, w);
+          if (tok_aux(pv) != 4 || w[0] != 0x6C6C756Eu) return false;  // null
+          checked += 4;
+        } else if (pc != T_STRING && pc != T_STRING_ESC) {
+          return false;
+        }
+        if (pf & TF_COLON) return false;
+        need_key = pf != 0;
+        if (!need_key) {
+          v = next();
+          break;
+        }
+      }
+      if (need_key || tok_cls(v) != T_OBJ_CLOSE) return false;
+    }
+    const uint32_t vf = v & TF_MASK;
+    if (vf & TF_COLON) return false;
+    comma = vf != 0;
+  }
+  if (comma) return false;  // a member the shape does not have
+  // the file object and the line's object close, and nothing follows
+  if ((next() & CF) != T_OBJ_CLOSE || (next() & CF) != T_OBJ_CLOSE || t != nt) return false;
+  if (tz.sc_bytes != checked) return false;  // a scalar byte no token covers
+  out.kind = kind;
+  out.flags = flags;
+  out.hard = 0;
+  out.path_off = path_off;
+  out.path_len = path_len;
+  out.size = size;
+  out.delts = delts;
+  return true;
 }
 
 // Whole-line walk (phases interleaved per window): the host reference and the General kernel.

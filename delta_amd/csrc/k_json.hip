@@ -234,6 +234,11 @@ constexpr int JL_FLUSH = DR_JL_FLUSH;
 #ifndef DR_JL_WAVES
 #define DR_JL_WAVES 1
 #endif
+// The bulk instantiation's 10 KiB of LDS per wave give 4 waves/SIMD; its registers are held to that
+// occupancy (128 VGPRs: it compiles to that without spilling, and to 141 when left free).
+#ifndef DR_JL_BULK_WAVES
+#define DR_JL_BULK_WAVES 4
+#endif
 // Small segments (a streamed commit: at most JL_SMALL_LINES lines) take the staged walker: each
 // wave copies its lines' byte region into LDS with coalesced 16-byte loads and every lane walks its
 // line from LDS, so the walk's dependent reads cost LDS latency instead of a global round trip each
@@ -252,7 +257,7 @@ template <bool InlineHard = false>
 __device__ __forceinline__ void walk_line(const JsonParseArgs& a, uint32_t* tokbuf, uint32_t lane, uint64_t line,
                                           bool live, uint64_t b, uint32_t n, const uint8_t* p) {
   jl::Tokenizer tz;
-  jl::Dfa<false> d;
+  jl::LineOut o;
   if (!live) tz.status = jl::ST_BAD;
   else if (n > jl::TOK_MAX_LINE) tz.status = jl::ST_HARD;
   const uint32_t o0 = uint32_t(b & 15);
@@ -267,6 +272,15 @@ __device__ __forceinline__ void walk_line(const JsonParseArgs& a, uint32_t* tokb
     tokbuf[nt * JL_T + lane] = t;
     ++nt;
   };
+  // A wave that reaches its last flush without an earlier one (no lane passed the flush mark: every
+  // line of config 3 has 20 tokens) holds every lane's whole token column, so each lane first tries
+  // the writer-shape matcher (json_lane.h) and only the lanes it declines step the DFA over the same
+  // tokens. The DFA is still in its initial state there and is constructed again after the matcher,
+  // so none of its state is live across it. A wave that flushed mid-line (one of its lines has more
+  // than JL_FLUSH tokens) keeps the DFA for all its lanes.
+  jl::Dfa<false> d;
+  bool flushed = false;  // wave-uniform: an earlier flush ran the DFA
+  bool matched = false;
   for (uint32_t j = 0;; ++j) {
     if (j < nwin && tz.status == jl::ST_OK) {
       uint32_t w[4];
@@ -292,19 +306,27 @@ __device__ __forceinline__ void walk_line(const JsonParseArgs& a, uint32_t* tokb
     const bool more = j + 1 < nwin && tz.status == jl::ST_OK;
     const bool anymore = __ballot(more) != 0ull;
     if (!anymore || __ballot(nt > uint32_t(JL_FLUSH)) != 0ull) {
-      uint32_t mx = nt;
-      for (int o = 32; o > 0; o >>= 1) mx = max(mx, uint32_t(__shfl_xor(int(mx), o, 64)));
 #if !defined(DR_JL_EXP)  // DR_JL_EXP: timing experiments only (scripts/build_variant.sh), no DFA
-      for (uint32_t t = 0; t < mx; ++t)
-        if (t < nt && d.status == jl::ST_OK) jl::dfa_token<false>(p, tokbuf[t * JL_T + lane], d);
+      bool need = true;  // this lane steps the DFA
+      if (!anymore && !flushed) {
+        matched = live && jl::match_writer_line(p, n, tokbuf + lane, JL_T, nt, tz, o);
+        need = live && !matched;
+        d = jl::Dfa<false>();
+      }
+      if (__ballot(need) != 0ull) {
+        uint32_t mx = need ? nt : 0u;
+        for (int s = 32; s > 0; s >>= 1) mx = max(mx, uint32_t(__shfl_xor(int(mx), s, 64)));
+        for (uint32_t t = 0; t < mx; ++t)
+          if (need && t < nt && d.status == jl::ST_OK) jl::dfa_token<false>(p, tokbuf[t * JL_T + lane], d);
+      }
 #endif
       nt = 0;
+      flushed = true;
     }
     if (!anymore) break;
   }
   if (!live) return;
-  jl::LineOut o;
-  jl::dfa_finish<false>(tz, d, o);
+  if (!matched) jl::dfa_finish<false>(tz, d, o);
   if (o.hard) {
     if constexpr (InlineHard) {
       const uint8_t* gp = a.buf + b;
@@ -772,7 +794,7 @@ __device__ __forceinline__ void tape_lines(const JsonParseArgs& a, uint64_t line
 //     diverging byte by byte.
 // The buffer is flushed through phase 2 whenever a lane could overflow it, and at the end.
 template <bool Stage>
-__global__ void __launch_bounds__(JL_T, DR_JL_WAVES) k_json_lines(JsonParseArgs a) {
+__global__ void __launch_bounds__(JL_T, Stage ? DR_JL_WAVES : DR_JL_BULK_WAVES) k_json_lines(JsonParseArgs a) {
   __shared__ uint32_t tokbuf[Stage ? 1 : JL_TOKCAP * JL_T];
   __shared__ uint4 stage[Stage ? JL_STAGE_BYTES / 16 : 1];
   __shared__ uint32_t tape[Stage ? TAPE_CAP : 1];
