@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "common.h"
+#include "deflate_fmt.h"
 #include "json_host.h"
 #include "kernels.h"
 #include "like_lane.h"
@@ -603,6 +604,10 @@ struct PagePlan {
   DBuf<uint32_t> d_wg_chunk0;
   uint64_t snap_in_bytes = 0, snap_out_bytes = 0, copy_bytes = 0;
   uint64_t snap_elements = 0;  // SNAPPY elements of the pages (known after a timed replay)
+  // GZIP pages (k_inflate): one wave each; nothing is allocated or launched for a plan without one
+  std::vector<InflatePage> gz_pages;
+  DBuf<InflatePage> d_gz;
+  uint64_t gz_in_bytes = 0, gz_out_bytes = 0;
   // PLAIN BYTE_ARRAY boundary scratch (k_ba_bounds)
   uint32_t ba_pages = 0;
   uint64_t ba_vals = 0;
@@ -1036,7 +1041,7 @@ static void plan_pages(StagedData& s, PagePlan& P) {
         const pq::ColumnChunk* cc = nullptr;
         for (auto& x : rg.cols) if (x.path == P.paths[c]) cc = &x;
         if (!cc) continue;
-        if (cc->codec != 0 && cc->codec != 1)
+        if (cc->codec != 0 && cc->codec != 1 && cc->codec != 2)
           fail(DR_E_UNSUPPORTED, fmt("checkpoint codec %d is not supported (column %s)", cc->codec, P.paths[c].c_str()));
         const pq::Leaf* l = part.meta.leaf(P.paths[c]);
         if (!l) fail(DR_E_PARQUET, fmt("checkpoint parts disagree on column %s", P.paths[c].c_str()));
@@ -1111,10 +1116,23 @@ static void plan_pages(StagedData& s, PagePlan& P) {
     const uint64_t lv = d.kind == PG_DATA_V2 ? uint64_t(d.v2_def_len + d.v2_rep_len) : 0;
     if (lv) P.copy_jobs.push_back(CopyJob{d.src, d.dst, lv});
     P.copy_bytes += lv;
-    const bool compressed = d.codec == 1 && !(d.kind == PG_DATA_V2 && !d.v2_compressed);
+    const bool compressed = d.codec != 0 && !(d.kind == PG_DATA_V2 && !d.v2_compressed);
     if (!compressed) {
       P.copy_jobs.push_back(CopyJob{d.src + lv, d.dst + lv, d.usize - lv});
       P.copy_bytes += d.usize - lv;
+      continue;
+    }
+    if (d.codec == 2) {  // GZIP: the first member's header is checked here, the rest on the device
+      const std::string& col = P.paths[size_t(d.col)];
+      if (lv > d.csize || lv > d.usize) fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", col.c_str()));
+      const uint32_t n_in = uint32_t(d.csize - lv), n_out = uint32_t(d.usize - lv);
+      if (n_in == 0 && n_out == 0) continue;
+      uint64_t at = 0;
+      if (dfl::gz_header(dfl::PtrSrc{s.h_pq.data() + d.src + lv, n_in}, at) != dfl::E_OK)
+        fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", col.c_str()));
+      P.gz_pages.push_back(InflatePage{d.src + lv, d.dst + lv, n_in, n_out, uint32_t(&d - P.pages.data()), 0});
+      P.gz_in_bytes += n_in;
+      P.gz_out_bytes += n_out;
       continue;
     }
     const uint8_t* h = s.h_pq.data() + d.src + lv;
@@ -1172,6 +1190,7 @@ static void plan_pages(StagedData& s, PagePlan& P) {
   P.d_arena = DBuf<uint8_t>(s.ctx, arena + 4096);
   const uint64_t pqb = reinterpret_cast<uint64_t>(s.d_pq.p), arb = reinterpret_cast<uint64_t>(P.d_arena.p);
   for (SnapPage& sp : P.snap_pages) { sp.in += pqb; sp.out += arb; }
+  for (InflatePage& gp : P.gz_pages) { gp.in += pqb; gp.out += arb; }
   for (CopyJob& j : P.copy_jobs) { j.src += pqb; j.dst += arb; }
   auto up = [&](auto& dbuf, auto& vec) {
     using T = typename std::decay_t<decltype(vec)>::value_type;
@@ -1180,6 +1199,7 @@ static void plan_pages(StagedData& s, PagePlan& P) {
       HIP_OK(hipMemcpyAsync(dbuf.p, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice, s.ctx->stream));
   };
   up(P.d_snap, P.snap_pages);
+  if (!P.gz_pages.empty()) up(P.d_gz, P.gz_pages);
   up(P.d_chunk_base, P.chunk_base);
   up(P.d_chunk_page, P.chunk_page);
   up(P.d_block_page, P.block_page);
@@ -1241,6 +1261,21 @@ static uint64_t scan_scratch_for(uint64_t n) {
   return b;
 }
 static ScanScratch ss(const DBuf<uint8_t>& b) { return ScanScratch{b.p, b.n}; }
+
+// What a decode's two error words say (decode_pages' `err`: [0] the page decoders' code, [1] the GZIP
+// inflater's ~(index of the first page it refused)): fails with DR_E_PARQUET if either is set.
+static void pq_error(const PagePlan& P, uint32_t code, uint32_t gz, const std::string& what) {
+  if (gz != 0) {
+    const uint32_t k = ~gz;
+    const char* col = k < P.gz_pages.size() ? P.paths[size_t(P.pages[P.gz_pages[k].page].col)].c_str() : "?";
+    fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", col));
+  }
+  if (code != 0) fail(DR_E_PARQUET, fmt("%s failed (code %u)", what.c_str(), code));
+}
+static void pq_error(const PagePlan& P, const DBuf<uint32_t>& err, hipStream_t stream, const std::string& what) {
+  const std::vector<uint32_t> w = d2h(err.p, 2, stream);
+  pq_error(P, w[0], w[1], what);
+}
 
 static void decode_pages(dr_ctx* ctx, PagePlan& P, ParquetArgs& pa, DBuf<uint64_t>& dict_ptr, DBuf<uint32_t>& dict_len,
                          DBuf<uint32_t>& err, void*) {
@@ -1390,6 +1425,8 @@ static void decode_pages(dr_ctx* ctx, PagePlan& P, ParquetArgs& pa, DBuf<uint64_
       }
     }
   }
+  // err[1]: the GZIP inflater's first-error word (see pq_error)
+  if (!P.gz_pages.empty()) launch_inflate(P.d_gz.p, uint32_t(P.gz_pages.size()), err.p + 1, stream);
   if (P.ba_pages) {
     launch_ba_bounds(pa, stream, scratch);
     if (std::getenv("DR_BA_DEBUG")) {
@@ -1964,7 +2001,7 @@ static ParsePending parse_launch(dr_ctx* ctx, const std::shared_ptr<StagedData>&
       }
       pa.cols[c] = FlatColumn{cdefs.p + uint64_t(c) * R, nullptr, cival[c].p, csptr[c].p, cslen[c].p};
     }
-    pq_err = DBuf<uint32_t>(ctx, 1);
+    pq_err = DBuf<uint32_t>(ctx, 2);
     pq_err.zero(stream);
     decode_pages(ctx, s.hot, pa, dict_ptr, dict_len, pq_err, scratch.p);
     CkptAssembleArgs ca{};
@@ -1990,7 +2027,8 @@ static ParsePending parse_launch(dr_ctx* ctx, const std::shared_ptr<StagedData>&
     HIP_OK(hipStreamWaitEvent(stream, ov.done, 0));
   }
   // the checkpoint decoder's error code rides in counters[7]: one read-back for both
-  if (R) HIP_OK(hipMemcpyAsync(counters.p + 7, pq_err.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+  // (with the GZIP inflater's error word in its upper half)
+  if (R) HIP_OK(hipMemcpyAsync(counters.p + 7, pq_err.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
   // ---- canonicalisation of special paths ----
   if (canonicalize) {
     DR_STAGE("canonicalize", stream);
@@ -2075,7 +2113,7 @@ static bool parse_finish(dr_ctx* ctx, const std::shared_ptr<StagedData>& sp, dr_
   StagedData& s = *sp;
   const uint64_t* cnt = ctx->pinned() + pp.pin_at;
   const uint64_t R = pp.R, nlines = pp.nlines, json_len = s.h_json.size();
-  if (R && cnt[7] != 0) fail(DR_E_PARQUET, fmt("device checkpoint decode failed (code %u)", unsigned(cnt[7])));
+  if (R && cnt[7] != 0) pq_error(s.hot, uint32_t(cnt[7]), uint32_t(cnt[7] >> 32), "device checkpoint decode");
   st->counts.malformed_lines = int64_t(cnt[3]);
   if (pp.canonicalize) {
     const uint64_t need = cnt[0] ? cnt[1] * 2 + 64 * cnt[0] + 64 : 0;
@@ -2902,11 +2940,10 @@ static void decode_export_side(dr_state& st, int which, ExpDecoded& D) {
     pa.cols[c] = FlatColumn{D.def[c].p, D.rep[c].p, D.ival[c].p, D.sptr[c].p, D.slen[c].p};
   }
   DBuf<uint64_t> dict_ptr;
-  DBuf<uint32_t> dict_len, pq_err(ctx, 1);
+  DBuf<uint32_t> dict_len, pq_err(ctx, 2);
   pq_err.zero(stream);
   decode_pages(ctx, P, pa, dict_ptr, dict_len, pq_err, nullptr);
-  if (d2h_one(pq_err.p, stream) != 0)
-    fail(DR_E_PARQUET, fmt("device decode of the %sexport columns failed (code %u)", pre.c_str(), d2h_one(pq_err.p, stream)));
+  pq_error(P, pq_err, stream, "device decode of the " + pre + "export columns");
   for (int c = 0; c < 4; ++c) {
     if (!P.present[c]) continue;
     if (P.levels[c] != R) fail(DR_E_PARQUET, pre + kExpLeaf[c] + ": one value per checkpoint row expected");
@@ -3414,7 +3451,7 @@ static void build_pv_columns(dr_state& st, const std::vector<std::pair<std::stri
   // the decoded entries are freed once the typed columns are built)
   DBuf<uint8_t> kdef, krep, vdef, vrep;
   DBuf<uint64_t> kptr, vptr, row_start, dict_ptr, rpos;
-  DBuf<uint32_t> klen, vlen, dict_len, pq_err(ctx, 1), rflag;
+  DBuf<uint32_t> klen, vlen, dict_len, pq_err(ctx, 2), rflag;
   DBuf<uint8_t> scratch(ctx, scan_scratch_for(0));
   pq_err.zero(stream);
   if (R && n) {
@@ -3441,8 +3478,7 @@ static void build_pv_columns(dr_state& st, const std::vector<std::pair<std::stri
       pa.cols[1] = FlatColumn{vdef.p, vrep.p, nullptr, vptr.p, vlen.p};
       if (scratch.n < scan_scratch_for(E)) scratch = DBuf<uint8_t>(ctx, scan_scratch_for(E));
       decode_pages(ctx, P, pa, dict_ptr, dict_len, pq_err, scratch.p);
-      if (d2h_one(pq_err.p, stream) != 0)
-        fail(DR_E_PARQUET, fmt("device decode of add.partitionValues failed (code %u)", d2h_one(pq_err.p, stream)));
+      pq_error(P, pq_err, stream, "device decode of add.partitionValues");
       rflag = DBuf<uint32_t>(ctx, E);
       rpos = DBuf<uint64_t>(ctx, E + 1);
       launch_rep0_flags(krep.p, E, rflag.p, stream);
@@ -4635,7 +4671,7 @@ static std::vector<int64_t> scan_order(dr_state& st) {
   DBuf<uint8_t> cdef;
   DBuf<int64_t> cval;
   DBuf<uint64_t> dict_ptr;
-  DBuf<uint32_t> dict_len, pq_err(ctx, 1);
+  DBuf<uint32_t> dict_len, pq_err(ctx, 2);
   pq_err.zero(stream);
   if (R) {
     {
@@ -4657,8 +4693,7 @@ static std::vector<int64_t> scan_order(dr_state& st) {
       pa.ncols = 1;
       pa.cols[0] = FlatColumn{cdef.p, nullptr, cval.p, nullptr, nullptr};
       decode_pages(ctx, P, pa, dict_ptr, dict_len, pq_err, nullptr);
-      if (d2h_one(pq_err.p, stream) != 0)
-        fail(DR_E_PARQUET, fmt("device decode of add.modificationTime failed (code %u)", d2h_one(pq_err.p, stream)));
+      pq_error(P, pq_err, stream, "device decode of add.modificationTime");
       a.ck_def = cdef.p;
       a.ck_val = cval.p;
       a.ck_max_def = P.max_def[0];
@@ -5658,12 +5693,13 @@ int dr_staged_plan(const dr_staged* staged, uint64_t* out, int32_t cap, int32_t*
   for (auto& p : s.parts) ck += p.len;
   for (auto& p : s.hot.pages) { cs += p.csize; us += p.usize; }
   const PagePlan& h = s.hot;
-  const uint64_t v[18] = {s.h_json.size(), ck, s.ck_rows, s.hot.pages.size(), cs, us, s.hot.dict_entries,
+  const uint64_t v[21] = {s.h_json.size(), ck, s.ck_rows, s.hot.pages.size(), cs, us, s.hot.dict_entries,
                           h.snap_in_bytes, h.snap_out_bytes, h.nchunks, h.block_page.size(), h.snap_elements,
                           h.copy_bytes, s.json_lines, h.dl_pages.size(), h.dl_sizings, h.dl_arena_bytes,
-                          0 /* DELTA_* pages decoded serially: there is no such decoder */};
+                          0 /* DELTA_* pages decoded serially: there is no such decoder */,
+                          h.gz_pages.size(), h.gz_in_bytes, h.gz_out_bytes};
   int32_t k = 0;
-  for (; k < cap && k < 18; ++k) out[k] = v[k];
+  for (; k < cap && k < 21; ++k) out[k] = v[k];
   *n = k;
   return DR_OK;
 }

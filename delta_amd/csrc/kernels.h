@@ -117,7 +117,7 @@ struct PageDesc {
   uint32_t num_values;   // levels in the page (= rows for flat columns)
   int32_t kind;          // PageKind
   int32_t encoding;
-  int32_t codec;         // 0 uncompressed, 1 snappy
+  int32_t codec;         // 0 uncompressed, 1 snappy, 2 gzip
   int32_t col;           // output column slot
   int32_t phys;          // physical type
   int32_t max_def;
@@ -230,6 +230,17 @@ uint32_t snappy_wg_chunks();
 uint32_t snappy_chunk_bytes();
 void launch_snappy(const SnappyArgs& a, hipStream_t st, ScanScratch scan_scratch);
 void launch_page_copy(const CopyJob* jobs, uint32_t njobs, hipStream_t st);
+
+// GZIP pages (k_inflate.hip): one wave per page. `in` is the page's compressed values (one or more
+// gzip members), `out` its slot in the arena; `page` indexes the page table. A page the kernel refuses
+// raises *error to ~(its index in `pages`), so that the lowest refused page is the one reported.
+struct InflatePage {
+  uint64_t in, out;      // device addresses
+  uint32_t n_in, n_out;
+  uint32_t page;
+  uint32_t pad_;
+};
+void launch_inflate(const InflatePage* pages, uint32_t npages, uint32_t* error, hipStream_t st);
 
 void launch_pq_dict(const ParquetArgs& a, hipStream_t st);
 void launch_pq_data(const ParquetArgs& a, hipStream_t st);

@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "delta_enc.h"
+#include "inflate_host.h"
 #include "snappy_host.h"
 
 namespace dr {
@@ -441,7 +442,7 @@ void delta_values(const uint8_t* p, const uint8_t* end, int enc, int type, int64
 }  // namespace
 
 HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChunk& cc, const Leaf& leaf) {
-  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY)
+  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP)
     fail(DR_E_UNSUPPORTED, fmt("codec %d not supported (column %s)", cc.codec, cc.path.c_str()));
   HostColumn col;
   HostColumn dict;
@@ -451,10 +452,14 @@ HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChu
     const uint8_t* body = file + pg.data_off;
     // DATA_PAGE_V2 keeps the level sections uncompressed in front of the (maybe compressed) values.
     int64_t lv = pg.page_type == DATA_PAGE_V2 ? pg.v2_def_len + pg.v2_rep_len : 0;
-    bool compressed = cc.codec == SNAPPY && !(pg.page_type == DATA_PAGE_V2 && !pg.v2_compressed);
+    bool compressed = cc.codec != UNCOMPRESSED && !(pg.page_type == DATA_PAGE_V2 && !pg.v2_compressed);
     buf.resize(size_t(pg.uncompressed_size));
     if (lv) memcpy(buf.data(), body, size_t(lv));
-    if (compressed) {
+    if (compressed && cc.codec == GZIP) {
+      if (dfl::inflate_members(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
+                               size_t(pg.uncompressed_size - lv)) != dfl::E_OK)
+        fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", cc.path.c_str()));
+    } else if (compressed) {
       if (!snappy_decompress(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)))
         fail(DR_E_PARQUET, fmt("corrupt snappy page in %s", cc.path.c_str()));
@@ -644,7 +649,7 @@ struct ValueStream {
 
 std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const ColumnChunk& cc, const Leaf& leaf,
                                   int thr, int64_t row_base) {
-  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY)
+  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP)
     fail(DR_E_UNSUPPORTED, fmt("codec %d not supported (column %s)", cc.codec, cc.path.c_str()));
   std::vector<Entry> out;
   HostColumn dict;
@@ -654,10 +659,14 @@ std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const Colum
   for (const Page& pg : walk_pages(file, len, cc)) {
     const uint8_t* body = file + pg.data_off;
     int64_t lv = pg.page_type == DATA_PAGE_V2 ? pg.v2_def_len + pg.v2_rep_len : 0;
-    bool compressed = cc.codec == SNAPPY && !(pg.page_type == DATA_PAGE_V2 && !pg.v2_compressed);
+    bool compressed = cc.codec != UNCOMPRESSED && !(pg.page_type == DATA_PAGE_V2 && !pg.v2_compressed);
     buf.resize(size_t(pg.uncompressed_size) + 16);
     if (lv) memcpy(buf.data(), body, size_t(lv));
-    if (compressed) {
+    if (compressed && cc.codec == GZIP) {
+      if (dfl::inflate_members(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
+                               size_t(pg.uncompressed_size - lv)) != dfl::E_OK)
+        fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", cc.path.c_str()));
+    } else if (compressed) {
       if (!snappy_decompress(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)))
         fail(DR_E_PARQUET, fmt("corrupt snappy page in %s", cc.path.c_str()));

@@ -248,7 +248,8 @@ class Staged:
         names = ["json_bytes", "checkpoint_bytes", "checkpoint_rows", "pages", "pages_compressed_bytes",
                  "pages_decompressed_bytes", "dict_entries", "snappy_in_bytes", "snappy_out_bytes",
                  "snappy_chunks", "snappy_blocks", "snappy_elements", "copy_bytes", "json_lines",
-                 "delta_pages", "delta_sizing_passes", "delta_arena_bytes", "delta_pages_serial"]
+                 "delta_pages", "delta_sizing_passes", "delta_arena_bytes", "delta_pages_serial",
+                 "gzip_pages", "gzip_in_bytes", "gzip_out_bytes"]
         return {names[i]: int(out[i]) for i in range(n.value)}
 
     def replay(self, min_file_retention_timestamp: int, validate: bool = True, reducer: str = "lds") -> "State":
