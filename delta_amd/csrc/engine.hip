@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "deflate_fmt.h"
+#include "zstd_fmt.h"
 #include "json_host.h"
 #include "kernels.h"
 #include "like_lane.h"
@@ -608,6 +609,11 @@ struct PagePlan {
   std::vector<InflatePage> gz_pages;
   DBuf<InflatePage> d_gz;
   uint64_t gz_in_bytes = 0, gz_out_bytes = 0;
+  // ZSTD pages (k_zstd): as the GZIP ones, plus the kernel's scratch (work counter and literal slabs)
+  std::vector<InflatePage> zs_pages;
+  DBuf<InflatePage> d_zs;
+  DBuf<uint8_t> d_zs_scratch;
+  uint64_t zs_in_bytes = 0, zs_out_bytes = 0;
   // PLAIN BYTE_ARRAY boundary scratch (k_ba_bounds)
   uint32_t ba_pages = 0;
   uint64_t ba_vals = 0;
@@ -1041,7 +1047,7 @@ static void plan_pages(StagedData& s, PagePlan& P) {
         const pq::ColumnChunk* cc = nullptr;
         for (auto& x : rg.cols) if (x.path == P.paths[c]) cc = &x;
         if (!cc) continue;
-        if (cc->codec != 0 && cc->codec != 1 && cc->codec != 2)
+        if (cc->codec != 0 && cc->codec != 1 && cc->codec != 2 && cc->codec != 6)
           fail(DR_E_UNSUPPORTED, fmt("checkpoint codec %d is not supported (column %s)", cc->codec, P.paths[c].c_str()));
         const pq::Leaf* l = part.meta.leaf(P.paths[c]);
         if (!l) fail(DR_E_PARQUET, fmt("checkpoint parts disagree on column %s", P.paths[c].c_str()));
@@ -1135,6 +1141,20 @@ static void plan_pages(StagedData& s, PagePlan& P) {
       P.gz_out_bytes += n_out;
       continue;
     }
+    if (d.codec == 6) {  // ZSTD: the first frame's header is checked here, the rest on the device
+      const std::string& col = P.paths[size_t(d.col)];
+      if (lv > d.csize || lv > d.usize) fail(DR_E_PARQUET, fmt("corrupt zstd page in %s", col.c_str()));
+      const uint32_t n_in = uint32_t(d.csize - lv), n_out = uint32_t(d.usize - lv);
+      if (n_in == 0 && n_out == 0) continue;
+      uint64_t at = 0;
+      zst::Frame f{};
+      if (n_in == 0 || zst::frame_header(zst::PtrSrc{s.h_pq.data() + d.src + lv, n_in}, n_in, at, &f) != zst::E_OK)
+        fail(DR_E_PARQUET, fmt("corrupt zstd page in %s", col.c_str()));
+      P.zs_pages.push_back(InflatePage{d.src + lv, d.dst + lv, n_in, n_out, uint32_t(&d - P.pages.data()), 0});
+      P.zs_in_bytes += n_in;
+      P.zs_out_bytes += n_out;
+      continue;
+    }
     const uint8_t* h = s.h_pq.data() + d.src + lv;
     uint64_t total = 0;
     uint32_t pre = 0;
@@ -1191,6 +1211,7 @@ static void plan_pages(StagedData& s, PagePlan& P) {
   const uint64_t pqb = reinterpret_cast<uint64_t>(s.d_pq.p), arb = reinterpret_cast<uint64_t>(P.d_arena.p);
   for (SnapPage& sp : P.snap_pages) { sp.in += pqb; sp.out += arb; }
   for (InflatePage& gp : P.gz_pages) { gp.in += pqb; gp.out += arb; }
+  for (InflatePage& zp : P.zs_pages) { zp.in += pqb; zp.out += arb; }
   for (CopyJob& j : P.copy_jobs) { j.src += pqb; j.dst += arb; }
   auto up = [&](auto& dbuf, auto& vec) {
     using T = typename std::decay_t<decltype(vec)>::value_type;
@@ -1200,6 +1221,10 @@ static void plan_pages(StagedData& s, PagePlan& P) {
   };
   up(P.d_snap, P.snap_pages);
   if (!P.gz_pages.empty()) up(P.d_gz, P.gz_pages);
+  if (!P.zs_pages.empty()) {
+    up(P.d_zs, P.zs_pages);
+    P.d_zs_scratch = DBuf<uint8_t>(s.ctx, zstd_scratch_bytes(uint32_t(P.zs_pages.size())));
+  }
   up(P.d_chunk_base, P.chunk_base);
   up(P.d_chunk_page, P.chunk_page);
   up(P.d_block_page, P.block_page);
@@ -1263,11 +1288,15 @@ static uint64_t scan_scratch_for(uint64_t n) {
 static ScanScratch ss(const DBuf<uint8_t>& b) { return ScanScratch{b.p, b.n}; }
 
 // What a decode's two error words say (decode_pages' `err`: [0] the page decoders' code, [1] the GZIP
-// inflater's ~(index of the first page it refused)): fails with DR_E_PARQUET if either is set.
+// inflater's and the ZSTD decoder's ~(index of the first page refused, the ZSTD jobs numbered after the GZIP
+// ones)): fails with DR_E_PARQUET if either is set.
 static void pq_error(const PagePlan& P, uint32_t code, uint32_t gz, const std::string& what) {
   if (gz != 0) {
     const uint32_t k = ~gz;
-    const char* col = k < P.gz_pages.size() ? P.paths[size_t(P.pages[P.gz_pages[k].page].col)].c_str() : "?";
+    const size_t ng = P.gz_pages.size();
+    if (k >= ng && k - ng < P.zs_pages.size())
+      fail(DR_E_PARQUET, fmt("corrupt zstd page in %s", P.paths[size_t(P.pages[P.zs_pages[k - ng].page].col)].c_str()));
+    const char* col = k < ng ? P.paths[size_t(P.pages[P.gz_pages[k].page].col)].c_str() : "?";
     fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", col));
   }
   if (code != 0) fail(DR_E_PARQUET, fmt("%s failed (code %u)", what.c_str(), code));
@@ -1427,6 +1456,8 @@ static void decode_pages(dr_ctx* ctx, PagePlan& P, ParquetArgs& pa, DBuf<uint64_
   }
   // err[1]: the GZIP inflater's first-error word (see pq_error)
   if (!P.gz_pages.empty()) launch_inflate(P.d_gz.p, uint32_t(P.gz_pages.size()), err.p + 1, stream);
+  if (!P.zs_pages.empty())
+    launch_zstd(P.d_zs.p, uint32_t(P.zs_pages.size()), uint32_t(P.gz_pages.size()), err.p + 1, P.d_zs_scratch.p, stream);
   if (P.ba_pages) {
     launch_ba_bounds(pa, stream, scratch);
     if (std::getenv("DR_BA_DEBUG")) {
@@ -5693,13 +5724,14 @@ int dr_staged_plan(const dr_staged* staged, uint64_t* out, int32_t cap, int32_t*
   for (auto& p : s.parts) ck += p.len;
   for (auto& p : s.hot.pages) { cs += p.csize; us += p.usize; }
   const PagePlan& h = s.hot;
-  const uint64_t v[21] = {s.h_json.size(), ck, s.ck_rows, s.hot.pages.size(), cs, us, s.hot.dict_entries,
+  const uint64_t v[24] = {s.h_json.size(), ck, s.ck_rows, s.hot.pages.size(), cs, us, s.hot.dict_entries,
                           h.snap_in_bytes, h.snap_out_bytes, h.nchunks, h.block_page.size(), h.snap_elements,
                           h.copy_bytes, s.json_lines, h.dl_pages.size(), h.dl_sizings, h.dl_arena_bytes,
                           0 /* DELTA_* pages decoded serially: there is no such decoder */,
-                          h.gz_pages.size(), h.gz_in_bytes, h.gz_out_bytes};
+                          h.gz_pages.size(), h.gz_in_bytes, h.gz_out_bytes,
+                          h.zs_pages.size(), h.zs_in_bytes, h.zs_out_bytes};
   int32_t k = 0;
-  for (; k < cap && k < 21; ++k) out[k] = v[k];
+  for (; k < cap && k < 24; ++k) out[k] = v[k];
   *n = k;
   return DR_OK;
 }

@@ -117,7 +117,7 @@ struct PageDesc {
   uint32_t num_values;   // levels in the page (= rows for flat columns)
   int32_t kind;          // PageKind
   int32_t encoding;
-  int32_t codec;         // 0 uncompressed, 1 snappy, 2 gzip
+  int32_t codec;         // 0 uncompressed, 1 snappy, 2 gzip, 6 zstd
   int32_t col;           // output column slot
   int32_t phys;          // physical type
   int32_t max_def;
@@ -241,6 +241,17 @@ struct InflatePage {
   uint32_t pad_;
 };
 void launch_inflate(const InflatePage* pages, uint32_t npages, uint32_t* error, hipStream_t st);
+
+// ZSTD pages (k_zstd.hip): the same job list, one workgroup of one wave per page; at most
+// ZSTD_MAX_WORKGROUPS workgroups take the pages from a counter, each with a slab for one block's
+// literals. `scratch` holds zstd_scratch_bytes(npages): the counter (zeroed by the launch) and the
+// slabs. A refused page raises *error to ~(first + its index in `pages`): the word is the GZIP
+// inflater's, and `first` is the number of GZIP jobs, so the lowest refused page of either is reported.
+constexpr uint32_t ZSTD_MAX_WORKGROUPS = 1024;
+constexpr uint32_t ZSTD_SLAB_BYTES = 128 * 1024 + 64;
+uint64_t zstd_scratch_bytes(uint32_t npages);
+void launch_zstd(const InflatePage* pages, uint32_t npages, uint32_t first, uint32_t* error, uint8_t* scratch,
+                 hipStream_t st);
 
 void launch_pq_dict(const ParquetArgs& a, hipStream_t st);
 void launch_pq_data(const ParquetArgs& a, hipStream_t st);

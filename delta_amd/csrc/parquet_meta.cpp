@@ -8,6 +8,7 @@
 #include "delta_enc.h"
 #include "inflate_host.h"
 #include "snappy_host.h"
+#include "zstd_host.h"
 
 namespace dr {
 namespace pq {
@@ -442,7 +443,7 @@ void delta_values(const uint8_t* p, const uint8_t* end, int enc, int type, int64
 }  // namespace
 
 HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChunk& cc, const Leaf& leaf) {
-  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP)
+  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP && cc.codec != ZSTD)
     fail(DR_E_UNSUPPORTED, fmt("codec %d not supported (column %s)", cc.codec, cc.path.c_str()));
   HostColumn col;
   HostColumn dict;
@@ -459,6 +460,10 @@ HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChu
       if (dfl::inflate_members(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                                size_t(pg.uncompressed_size - lv)) != dfl::E_OK)
         fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", cc.path.c_str()));
+    } else if (compressed && cc.codec == ZSTD) {
+      if (zst::decode_frames(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
+                             size_t(pg.uncompressed_size - lv)) != zst::E_OK)
+        fail(DR_E_PARQUET, fmt("corrupt zstd page in %s", cc.path.c_str()));
     } else if (compressed) {
       if (!snappy_decompress(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)))
@@ -649,7 +654,7 @@ struct ValueStream {
 
 std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const ColumnChunk& cc, const Leaf& leaf,
                                   int thr, int64_t row_base) {
-  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP)
+  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP && cc.codec != ZSTD)
     fail(DR_E_UNSUPPORTED, fmt("codec %d not supported (column %s)", cc.codec, cc.path.c_str()));
   std::vector<Entry> out;
   HostColumn dict;
@@ -666,6 +671,10 @@ std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const Colum
       if (dfl::inflate_members(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                                size_t(pg.uncompressed_size - lv)) != dfl::E_OK)
         fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", cc.path.c_str()));
+    } else if (compressed && cc.codec == ZSTD) {
+      if (zst::decode_frames(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
+                             size_t(pg.uncompressed_size - lv)) != zst::E_OK)
+        fail(DR_E_PARQUET, fmt("corrupt zstd page in %s", cc.path.c_str()));
     } else if (compressed) {
       if (!snappy_decompress(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)))

@@ -224,7 +224,8 @@ int dr_staged_bytes(const dr_staged* staged, uint64_t* json_bytes, uint64_t* che
  * [14] DELTA_* pages of the hot columns, [15] sizing passes run for their expansion arena (one read-back
  * each: 0 before the first replay or without DELTA_BYTE_ARRAY pages, then 1), [16] bytes of that arena,
  * [17] DELTA_* pages decoded serially (always 0: there is no serial decoder), [18] GZIP-compressed pages
- * of the hot columns, [19] their compressed bytes, [20] their decompressed bytes. *n receives the number of
+ * of the hot columns, [19] their compressed bytes, [20] their decompressed bytes, [21] ZSTD-compressed
+ * pages of the hot columns, [22] their compressed bytes, [23] their decompressed bytes. *n receives the number of
  * figures written (<= cap). */
 int dr_staged_plan(const dr_staged* staged, uint64_t* out, int32_t cap, int32_t* n);
 
