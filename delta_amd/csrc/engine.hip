@@ -36,6 +36,7 @@
 #include "common.h"
 #include "deflate_fmt.h"
 #include "zstd_fmt.h"
+#include "lz4_fmt.h"
 #include "json_host.h"
 #include "kernels.h"
 #include "like_lane.h"
@@ -614,6 +615,10 @@ struct PagePlan {
   DBuf<InflatePage> d_zs;
   DBuf<uint8_t> d_zs_scratch;
   uint64_t zs_in_bytes = 0, zs_out_bytes = 0;
+  // LZ4 pages (k_lz4), codecs 5 and 7 together: as the GZIP ones, the framing in InflatePage::pad_
+  std::vector<InflatePage> lz_pages;
+  DBuf<InflatePage> d_lz;
+  uint64_t lz_in_bytes = 0, lz_out_bytes = 0;
   // PLAIN BYTE_ARRAY boundary scratch (k_ba_bounds)
   uint32_t ba_pages = 0;
   uint64_t ba_vals = 0;
@@ -1047,7 +1052,7 @@ static void plan_pages(StagedData& s, PagePlan& P) {
         const pq::ColumnChunk* cc = nullptr;
         for (auto& x : rg.cols) if (x.path == P.paths[c]) cc = &x;
         if (!cc) continue;
-        if (cc->codec != 0 && cc->codec != 1 && cc->codec != 2 && cc->codec != 6)
+        if (cc->codec != 0 && cc->codec != 1 && cc->codec != 2 && cc->codec != 5 && cc->codec != 6 && cc->codec != 7)
           fail(DR_E_UNSUPPORTED, fmt("checkpoint codec %d is not supported (column %s)", cc->codec, P.paths[c].c_str()));
         const pq::Leaf* l = part.meta.leaf(P.paths[c]);
         if (!l) fail(DR_E_PARQUET, fmt("checkpoint parts disagree on column %s", P.paths[c].c_str()));
@@ -1155,6 +1160,55 @@ static void plan_pages(StagedData& s, PagePlan& P) {
       P.zs_out_bytes += n_out;
       continue;
     }
+    if (d.codec == 5 || d.codec == 7) {  // LZ4: the first unit's words are checked here, the rest on the device
+      const std::string& col = P.paths[size_t(d.col)];
+      if (lv > d.csize || lv > d.usize) fail(DR_E_PARQUET, fmt("corrupt lz4 page in %s", col.c_str()));
+      const uint32_t n_in = uint32_t(d.csize - lv), n_out = uint32_t(d.usize - lv);
+      const uint32_t framing = d.codec == 5 ? lz4::F_HADOOP : lz4::F_BARE;
+      if (framing == lz4::F_HADOOP && n_in == 0 && n_out == 0) continue;
+      const lz4::PtrSrc src{s.h_pq.data() + d.src + lv, n_in};
+      bool ok = n_in > 0;
+      if (ok && framing == lz4::F_HADOOP) {
+        uint64_t at = 0;
+        uint32_t U = 0, C = 0;
+        ok = lz4::unit_header(src, at, n_in, n_out, &U) == lz4::E_OK && lz4::inner_header(src, at, n_in, &C) == lz4::E_OK;
+      }
+      if (!ok) fail(DR_E_PARQUET, fmt("corrupt lz4 page in %s", col.c_str()));
+      {
+        // a page the compressor could not shrink is one literal run per block: those bytes are copied
+        // as they are. lz4::next takes the decision, so the verdict is the decoder's.
+        std::vector<CopyJob> lit;
+        uint64_t pos = 0, op = 0;
+        bool plain = true;
+        while (plain && pos < n_in) {
+          uint64_t at = pos, len = n_in, cap = n_out;
+          if (framing == lz4::F_HADOOP) {
+            uint32_t U = 0, C = 0;
+            plain = lz4::unit_header(src, at, n_in, n_out - op, &U) == lz4::E_OK &&
+                    lz4::inner_header(src, at, n_in, &C) == lz4::E_OK;
+            len = C;
+            cap = U;
+          }
+          lz4::Block b{};
+          lz4::Seq q{};
+          if (plain) lz4::begin(b, at, len, cap);
+          plain = plain && lz4::next(src, b, &q) == lz4::E_OK && q.last && q.ll == cap;
+          if (!plain) break;
+          if (q.ll) lit.push_back(CopyJob{d.src + lv + q.lit, d.dst + lv + op, q.ll});
+          op += q.ll;
+          pos = at + len;
+        }
+        if (plain && op == n_out) {
+          P.copy_jobs.insert(P.copy_jobs.end(), lit.begin(), lit.end());
+          P.copy_bytes += n_out;
+          continue;
+        }
+      }
+      P.lz_pages.push_back(InflatePage{d.src + lv, d.dst + lv, n_in, n_out, uint32_t(&d - P.pages.data()), framing});
+      P.lz_in_bytes += n_in;
+      P.lz_out_bytes += n_out;
+      continue;
+    }
     const uint8_t* h = s.h_pq.data() + d.src + lv;
     uint64_t total = 0;
     uint32_t pre = 0;
@@ -1212,6 +1266,7 @@ static void plan_pages(StagedData& s, PagePlan& P) {
   for (SnapPage& sp : P.snap_pages) { sp.in += pqb; sp.out += arb; }
   for (InflatePage& gp : P.gz_pages) { gp.in += pqb; gp.out += arb; }
   for (InflatePage& zp : P.zs_pages) { zp.in += pqb; zp.out += arb; }
+  for (InflatePage& lp : P.lz_pages) { lp.in += pqb; lp.out += arb; }
   for (CopyJob& j : P.copy_jobs) { j.src += pqb; j.dst += arb; }
   auto up = [&](auto& dbuf, auto& vec) {
     using T = typename std::decay_t<decltype(vec)>::value_type;
@@ -1225,6 +1280,7 @@ static void plan_pages(StagedData& s, PagePlan& P) {
     up(P.d_zs, P.zs_pages);
     P.d_zs_scratch = DBuf<uint8_t>(s.ctx, zstd_scratch_bytes(uint32_t(P.zs_pages.size())));
   }
+  if (!P.lz_pages.empty()) up(P.d_lz, P.lz_pages);
   up(P.d_chunk_base, P.chunk_base);
   up(P.d_chunk_page, P.chunk_page);
   up(P.d_block_page, P.block_page);
@@ -1288,14 +1344,17 @@ static uint64_t scan_scratch_for(uint64_t n) {
 static ScanScratch ss(const DBuf<uint8_t>& b) { return ScanScratch{b.p, b.n}; }
 
 // What a decode's two error words say (decode_pages' `err`: [0] the page decoders' code, [1] the GZIP
-// inflater's and the ZSTD decoder's ~(index of the first page refused, the ZSTD jobs numbered after the GZIP
-// ones)): fails with DR_E_PARQUET if either is set.
+// inflater's, the ZSTD decoder's and the LZ4 decoder's ~(index of the first page refused, the ZSTD jobs numbered
+// after the GZIP ones and the LZ4 jobs after both)): fails with DR_E_PARQUET if either is set.
 static void pq_error(const PagePlan& P, uint32_t code, uint32_t gz, const std::string& what) {
   if (gz != 0) {
     const uint32_t k = ~gz;
     const size_t ng = P.gz_pages.size();
     if (k >= ng && k - ng < P.zs_pages.size())
       fail(DR_E_PARQUET, fmt("corrupt zstd page in %s", P.paths[size_t(P.pages[P.zs_pages[k - ng].page].col)].c_str()));
+    const size_t nz = ng + P.zs_pages.size();
+    if (k >= nz && k - nz < P.lz_pages.size())
+      fail(DR_E_PARQUET, fmt("corrupt lz4 page in %s", P.paths[size_t(P.pages[P.lz_pages[k - nz].page].col)].c_str()));
     const char* col = k < ng ? P.paths[size_t(P.pages[P.gz_pages[k].page].col)].c_str() : "?";
     fail(DR_E_PARQUET, fmt("corrupt gzip page in %s", col));
   }
@@ -1458,6 +1517,8 @@ static void decode_pages(dr_ctx* ctx, PagePlan& P, ParquetArgs& pa, DBuf<uint64_
   if (!P.gz_pages.empty()) launch_inflate(P.d_gz.p, uint32_t(P.gz_pages.size()), err.p + 1, stream);
   if (!P.zs_pages.empty())
     launch_zstd(P.d_zs.p, uint32_t(P.zs_pages.size()), uint32_t(P.gz_pages.size()), err.p + 1, P.d_zs_scratch.p, stream);
+  if (!P.lz_pages.empty())
+    launch_lz4(P.d_lz.p, uint32_t(P.lz_pages.size()), uint32_t(P.gz_pages.size() + P.zs_pages.size()), err.p + 1, stream);
   if (P.ba_pages) {
     launch_ba_bounds(pa, stream, scratch);
     if (std::getenv("DR_BA_DEBUG")) {
@@ -5724,14 +5785,15 @@ int dr_staged_plan(const dr_staged* staged, uint64_t* out, int32_t cap, int32_t*
   for (auto& p : s.parts) ck += p.len;
   for (auto& p : s.hot.pages) { cs += p.csize; us += p.usize; }
   const PagePlan& h = s.hot;
-  const uint64_t v[24] = {s.h_json.size(), ck, s.ck_rows, s.hot.pages.size(), cs, us, s.hot.dict_entries,
+  const uint64_t v[27] = {s.h_json.size(), ck, s.ck_rows, s.hot.pages.size(), cs, us, s.hot.dict_entries,
                           h.snap_in_bytes, h.snap_out_bytes, h.nchunks, h.block_page.size(), h.snap_elements,
                           h.copy_bytes, s.json_lines, h.dl_pages.size(), h.dl_sizings, h.dl_arena_bytes,
                           0 /* DELTA_* pages decoded serially: there is no such decoder */,
                           h.gz_pages.size(), h.gz_in_bytes, h.gz_out_bytes,
-                          h.zs_pages.size(), h.zs_in_bytes, h.zs_out_bytes};
+                          h.zs_pages.size(), h.zs_in_bytes, h.zs_out_bytes,
+                          h.lz_pages.size(), h.lz_in_bytes, h.lz_out_bytes};
   int32_t k = 0;
-  for (; k < cap && k < 24; ++k) out[k] = v[k];
+  for (; k < cap && k < 27; ++k) out[k] = v[k];
   *n = k;
   return DR_OK;
 }

@@ -117,7 +117,7 @@ struct PageDesc {
   uint32_t num_values;   // levels in the page (= rows for flat columns)
   int32_t kind;          // PageKind
   int32_t encoding;
-  int32_t codec;         // 0 uncompressed, 1 snappy, 2 gzip, 6 zstd
+  int32_t codec;         // 0 uncompressed, 1 snappy, 2 gzip, 5 lz4 (hadoop), 6 zstd, 7 lz4_raw
   int32_t col;           // output column slot
   int32_t phys;          // physical type
   int32_t max_def;
@@ -238,7 +238,7 @@ struct InflatePage {
   uint64_t in, out;      // device addresses
   uint32_t n_in, n_out;
   uint32_t page;
-  uint32_t pad_;
+  uint32_t pad_;         // k_lz4: the framing
 };
 void launch_inflate(const InflatePage* pages, uint32_t npages, uint32_t* error, hipStream_t st);
 
@@ -252,6 +252,17 @@ constexpr uint32_t ZSTD_SLAB_BYTES = 128 * 1024 + 64;
 uint64_t zstd_scratch_bytes(uint32_t npages);
 void launch_zstd(const InflatePage* pages, uint32_t npages, uint32_t first, uint32_t* error, uint8_t* scratch,
                  hipStream_t st);
+
+// LZ4 pages (k_lz4.hip): the same job list, one workgroup of one wave per page; `pad_` holds the framing
+// (lz4::Framing: 0 one bare block, Parquet codec 7; 1 Hadoop units, codec 5). A refused page raises
+// *error to ~(first + its index in `pages`): the word is the GZIP inflater's, and `first` is the number
+// of GZIP and ZSTD jobs, so the lowest refused page of the three is reported. The kernel's output ring
+// holds the 64 KiB an offset reaches back plus the LZ4_ROUND_SPAN bytes a round adds, in which it
+// queues at most LZ4_ROUND_BATCH sequences (the tests place matches across both boundaries).
+constexpr uint32_t LZ4_RING_BYTES = 74752;
+constexpr uint32_t LZ4_ROUND_SPAN = LZ4_RING_BYTES - 65536;
+constexpr uint32_t LZ4_ROUND_BATCH = 128;
+void launch_lz4(const InflatePage* pages, uint32_t npages, uint32_t first, uint32_t* error, hipStream_t st);
 
 void launch_pq_dict(const ParquetArgs& a, hipStream_t st);
 void launch_pq_data(const ParquetArgs& a, hipStream_t st);

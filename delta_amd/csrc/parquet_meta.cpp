@@ -7,6 +7,7 @@
 #include "common.h"
 #include "delta_enc.h"
 #include "inflate_host.h"
+#include "lz4_host.h"
 #include "snappy_host.h"
 #include "zstd_host.h"
 
@@ -443,7 +444,8 @@ void delta_values(const uint8_t* p, const uint8_t* end, int enc, int type, int64
 }  // namespace
 
 HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChunk& cc, const Leaf& leaf) {
-  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP && cc.codec != ZSTD)
+  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP && cc.codec != ZSTD && cc.codec != LZ4 &&
+      cc.codec != LZ4_RAW)
     fail(DR_E_UNSUPPORTED, fmt("codec %d not supported (column %s)", cc.codec, cc.path.c_str()));
   HostColumn col;
   HostColumn dict;
@@ -464,6 +466,10 @@ HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChu
       if (zst::decode_frames(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)) != zst::E_OK)
         fail(DR_E_PARQUET, fmt("corrupt zstd page in %s", cc.path.c_str()));
+    } else if (compressed && (cc.codec == LZ4 || cc.codec == LZ4_RAW)) {
+      if (lz4::decode_page(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv, size_t(pg.uncompressed_size - lv),
+                           cc.codec == LZ4 ? lz4::F_HADOOP : lz4::F_BARE) != lz4::E_OK)
+        fail(DR_E_PARQUET, fmt("corrupt lz4 page in %s", cc.path.c_str()));
     } else if (compressed) {
       if (!snappy_decompress(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)))
@@ -654,7 +660,8 @@ struct ValueStream {
 
 std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const ColumnChunk& cc, const Leaf& leaf,
                                   int thr, int64_t row_base) {
-  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP && cc.codec != ZSTD)
+  if (cc.codec != UNCOMPRESSED && cc.codec != SNAPPY && cc.codec != GZIP && cc.codec != ZSTD && cc.codec != LZ4 &&
+      cc.codec != LZ4_RAW)
     fail(DR_E_UNSUPPORTED, fmt("codec %d not supported (column %s)", cc.codec, cc.path.c_str()));
   std::vector<Entry> out;
   HostColumn dict;
@@ -675,6 +682,10 @@ std::vector<Entry> sparse_entries(const uint8_t* file, uint64_t len, const Colum
       if (zst::decode_frames(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)) != zst::E_OK)
         fail(DR_E_PARQUET, fmt("corrupt zstd page in %s", cc.path.c_str()));
+    } else if (compressed && (cc.codec == LZ4 || cc.codec == LZ4_RAW)) {
+      if (lz4::decode_page(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv, size_t(pg.uncompressed_size - lv),
+                           cc.codec == LZ4 ? lz4::F_HADOOP : lz4::F_BARE) != lz4::E_OK)
+        fail(DR_E_PARQUET, fmt("corrupt lz4 page in %s", cc.path.c_str()));
     } else if (compressed) {
       if (!snappy_decompress(body + lv, size_t(pg.compressed_size - lv), buf.data() + lv,
                              size_t(pg.uncompressed_size - lv)))

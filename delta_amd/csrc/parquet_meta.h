@@ -13,7 +13,7 @@ namespace pq {
 enum PhysType { BOOLEAN = 0, INT32 = 1, INT64 = 2, INT96 = 3, FLOAT = 4, DOUBLE = 5, BYTE_ARRAY = 6,
                 FIXED_LEN_BYTE_ARRAY = 7 };
 enum Repetition { REQUIRED = 0, OPTIONAL = 1, REPEATED = 2 };
-enum Codec { UNCOMPRESSED = 0, SNAPPY = 1, GZIP = 2, ZSTD = 6 };
+enum Codec { UNCOMPRESSED = 0, SNAPPY = 1, GZIP = 2, LZ4 = 5, ZSTD = 6, LZ4_RAW = 7 };
 enum Encoding { PLAIN = 0, PLAIN_DICTIONARY = 2, RLE = 3, BIT_PACKED = 4, DELTA_BINARY_PACKED = 5,
                 DELTA_LENGTH_BYTE_ARRAY = 6, DELTA_BYTE_ARRAY = 7, RLE_DICTIONARY = 8 };
 enum PageType { DATA_PAGE = 0, INDEX_PAGE = 1, DICTIONARY_PAGE = 2, DATA_PAGE_V2 = 3 };
@@ -77,7 +77,7 @@ struct HostColumn {
   std::vector<int64_t> ivals;                 // INT32/INT64/BOOLEAN values (non-null only)
   std::vector<std::string> svals;             // BYTE_ARRAY values (non-null only)
 };
-// Decodes every page of one column chunk (any codec we support: UNCOMPRESSED, SNAPPY, GZIP, ZSTD).
+// Decodes every page of one column chunk (any codec we support: UNCOMPRESSED, SNAPPY, GZIP, ZSTD, LZ4, LZ4_RAW).
 HostColumn decode_column_host(const uint8_t* file, uint64_t len, const ColumnChunk& cc,
                               const Leaf& leaf);
 

@@ -250,7 +250,8 @@ class Staged:
                  "snappy_chunks", "snappy_blocks", "snappy_elements", "copy_bytes", "json_lines",
                  "delta_pages", "delta_sizing_passes", "delta_arena_bytes", "delta_pages_serial",
                  "gzip_pages", "gzip_in_bytes", "gzip_out_bytes",
-                 "zstd_pages", "zstd_in_bytes", "zstd_out_bytes"]
+                 "zstd_pages", "zstd_in_bytes", "zstd_out_bytes",
+                 "lz4_pages", "lz4_in_bytes", "lz4_out_bytes"]
         return {names[i]: int(out[i]) for i in range(n.value)}
 
     def replay(self, min_file_retention_timestamp: int, validate: bool = True, reducer: str = "lds") -> "State":

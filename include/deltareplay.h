@@ -225,8 +225,10 @@ int dr_staged_bytes(const dr_staged* staged, uint64_t* json_bytes, uint64_t* che
  * each: 0 before the first replay or without DELTA_BYTE_ARRAY pages, then 1), [16] bytes of that arena,
  * [17] DELTA_* pages decoded serially (always 0: there is no serial decoder), [18] GZIP-compressed pages
  * of the hot columns, [19] their compressed bytes, [20] their decompressed bytes, [21] ZSTD-compressed
- * pages of the hot columns, [22] their compressed bytes, [23] their decompressed bytes. *n receives the number of
- * figures written (<= cap). */
+ * pages of the hot columns, [22] their compressed bytes, [23] their decompressed bytes, [24] LZ4-compressed pages
+ * of the hot columns (codecs 5, Hadoop-framed LZ4, and 7, LZ4_RAW, together; a page that holds nothing but
+ * literals is a copy and counts under [12]), [25] their compressed bytes, [26] their decompressed bytes. *n
+ * receives the number of figures written (<= cap). */
 int dr_staged_plan(const dr_staged* staged, uint64_t* out, int32_t cap, int32_t* n);
 
 /* ---- replay (device) ----------------------------------------------------------------------
