@@ -686,7 +686,9 @@ __global__ void __launch_bounds__(SCAN_T) k_snap_scan(SnappyArgs a) {
 // Every element of the chunk range is checked (a copy reaching before its fragment, an element
 // straddling a block, literal bytes past the page) and the block's elements must cover it exactly;
 // anything else -- or a block of more than EXEC_EMAX * 1024 elements or 128 KiB of compressed
-// input, which the SNAPPY compressor's output never has -- flags the page for k_snap_serial.
+// input, which the SNAPPY compressor's output never has -- flags the page for k_snap_serial. Both
+// limits count the block's whole chunk range: the elements of its neighbours that start in its first
+// and last chunk are among the EXEC_EMAX * 1024, their bytes among the 128 KiB.
 constexpr int EXEC_T = 1024;
 #ifndef DR_EXEC_EMAX
 #define DR_EXEC_EMAX 32
@@ -899,11 +901,12 @@ __global__ void __launch_bounds__(EXEC_T) k_snap_exec(SnappyArgs a) {
         const uint32_t hdr = ((0x5320u >> (4u * ty)) & 15u) + sel(lit, 1u + nb, 0u);  // 1 + nb, 2, 3, 5
         const uint32_t off = sel(c1, ((tag >> 5) << 8) | (w8 & 0xffu), w8 & 0xffffu);
         const uint32_t adv = hdr + sel(lit, len, 0u);
-        // a literal past the page or longer than a fragment, a copy offset no fragment has (copy-4's
-        // upper offset bytes): the page is not one the parallel path can take
-        const bool bad_lit = (len > SNAP_BLOCK) | (uint64_t(pos) + adv > n_in);
+        // an element past the page (a literal's bytes, or a header cut off by the page's end), a literal
+        // longer than a fragment (or of 2^32 bytes, which is 0 here: len - 1 wraps), a copy offset no
+        // fragment has (copy-4's upper offset bytes): the page is not one the parallel path can take
+        const bool bad_lit = len - 1u >= SNAP_BLOCK;
         const bool bad_cp = (ty == 3u) & ((w8 >> 16) != 0u);
-        bad |= (so > so_lim) | (lit & bad_lit) | (!lit & bad_cp);
+        bad |= (so > so_lim) | (uint64_t(pos) + adv > n_in) | (lit & bad_lit) | (!lit & bad_cp);
         el[k] = (hdr << 24) | sel(lit, EL_LIT | ((len - 1u) & 0xffffu), ((len - 1u) << 16) | off);
         sum += sel(lit, min(len, SNAP_BLOCK), len);
         pos += adv;
@@ -1214,7 +1217,9 @@ __global__ void k_snap_serial(SnappyArgs a) {
   uint64_t ip = 0, op = 0;
   while (ip < pg.n_in) {
     const Elem el = snap_elem(in + ip);
-    if (op + el.len > pg.n_out) { atomicCAS(a.error, 0u, 1u); return; }
+    // a header cut off by the page's end (its missing bytes were read from behind the page), a literal of
+    // 2^32 bytes (0 in 32 bits), output past the page
+    if (ip + el.hdr > pg.n_in || el.len == 0 || op + el.len > pg.n_out) { atomicCAS(a.error, 0u, 1u); return; }
     if ((in[ip] & 3u) == 0) {  // literal (a copy with offset 0 is corrupt, below)
       if (ip + el.hdr + el.len > pg.n_in) { atomicCAS(a.error, 0u, 1u); return; }
       for (uint32_t i = 0; i < el.len; ++i) out[op + i] = in[ip + el.hdr + i];

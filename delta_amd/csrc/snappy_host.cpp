@@ -5,10 +5,11 @@
 namespace dr {
 
 bool snappy_uncompressed_length(const uint8_t* in, size_t n, uint64_t* out) {
+  // a varint of at most 5 bytes holding at most 32 bits, as the format has it (libsnappy refuses more)
   uint64_t v = 0;
-  for (size_t i = 0; i < n && i < 10; ++i) {
+  for (size_t i = 0; i < n && i < 5; ++i) {
     v |= uint64_t(in[i] & 0x7f) << (7 * i);
-    if (!(in[i] & 0x80)) { *out = v; return true; }
+    if (!(in[i] & 0x80)) { *out = v; return v <= 0xffffffffull; }
   }
   return false;
 }

@@ -498,13 +498,16 @@ def is_literals_only(body, n_out, codec):
                                for U, bl in units for p, c in bl)
 
 
-def rewrite(path, out, bodies=None, chunk_codecs=None, body_of=None):
+def rewrite(path, out, bodies=None, chunk_codecs=None, body_of=None, stored=()):
     """Writes `out`: `path` with page bodies replaced. bodies: {(leaf, page index over all row groups):
     (codec, body)} for the compressed part of a page; chunk_codecs: {leaf: codec} for the footer;
     body_of(leaf, index, codec, body, uncompressed length) -> body or None, asked for every compressed
     page that `bodies` does not name. Page headers get the new compressed_page_size; the footer gets each
     chunk's codec, total_compressed_size, page offsets and file_offset, and each row group's
-    total_compressed_size and file_offset."""
+    total_compressed_size and file_offset. stored: leaves whose DATA_PAGE_V2 pages the writer left
+    uncompressed (is_compressed false) count as compressed pages too; one that gets a body is marked
+    compressed. The header must hold is_compressed, as pyarrow's do: one that leaves the field to its default
+    raises KeyError here."""
     bodies, chunk_codecs = bodies or {}, chunk_codecs or {}
     buf = open(path, "rb").read()
     meta, chunks = _chunks(buf)
@@ -521,7 +524,7 @@ def rewrite(path, out, bodies=None, chunk_codecs=None, body_of=None):
             for h, pos, lv, compressed in _pages(buf, start, end):
                 k = seen.get(leaf, 0)
                 body = buf[pos:pos + _get(h, 3)]
-                if compressed:
+                if compressed or (leaf in stored and _get(h, 8) is not None):
                     seen[leaf] = k + 1
                     repl = bodies.get((leaf, k))
                     if repl is None and body_of is not None:
@@ -531,6 +534,8 @@ def rewrite(path, out, bodies=None, chunk_codecs=None, body_of=None):
                         assert repl[0] == codec, "page %d of %s is codec %d in a chunk of codec %d" % (k, leaf, repl[0], codec)
                         body = body[:lv] + repl[1]
                         _set(h, 3, len(body))
+                        if not compressed:
+                            _set(_get(h, 8), 7, True)
                 if _get(h, 1) == 2:
                     dict_off = len(new)
                 elif data_off is None:
