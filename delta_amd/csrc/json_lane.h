@@ -338,14 +338,22 @@ struct Tokenizer {
   uint32_t sc_bytes = 0;     // scalar bytes seen (each must belong to a validated scalar)
   uint32_t str_open = 0;     // line offset of the open string's quote
   uint32_t pend = TOK_NONE;  // the line's latest token, held back for a ':' / ',' that may follow
+  // A token's offset field has 16 bits. The General walker also takes lines over TOK_MAX_LINE, so the
+  // whole offset of every token travels beside it: pend_off is pend's, out_off that of the token being
+  // handed to emit. Only parse_line_t<true> reads them; in the fast walker they are dead.
+  uint32_t pend_off = 0, out_off = 0;
   uint8_t status = ST_OK;
 };
 
 // The next token of the line: the one held back goes out, this one waits for its punctuation.
 template <typename Emit>
-JL_HD void tok_put(Tokenizer& tz, uint32_t t, Emit&& emit) {
-  if (tz.pend != TOK_NONE) emit(tz.pend);
+JL_HD void tok_put(Tokenizer& tz, uint32_t t, uint32_t off, Emit&& emit) {
+  if (tz.pend != TOK_NONE) {
+    tz.out_off = tz.pend_off;
+    emit(tz.pend);
+  }
   tz.pend = t;
+  tz.pend_off = off;
 }
 
 // Loads the aligned 16-byte window at a (a is 16-byte aligned; the buffer is readable there).
@@ -431,7 +439,7 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
     const uint32_t end = uint32_t(lo);  // one past the run
     const uint32_t len = end - tz.sc_start;
     if (len > TOK_MAX_SCALAR) { tz.status = ST_BAD; return; }
-    tok_put(tz, tok_scalar(tz.sc_start, len), emit);
+    tok_put(tz, tok_scalar(tz.sc_start, len), tz.sc_start, emit);
   }
   const uint32_t sc_begin = sc & ~(((sc << 1) | tz.sc_carry) & 0xFFFFu);
   const uint32_t sc_end = sc & ~(sc >> 1) & 0x7FFFu;  // run ends inside this window
@@ -465,10 +473,10 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
       }
       const uint32_t len = off - open_off - 1u;
       if (len <= TOK_MAX_AUX) {
-        tok_put(tz, tok_make(open_off, len, has_bs ? T_STRING_ESC : T_STRING), emit);
+        tok_put(tz, tok_make(open_off, len, has_bs ? T_STRING_ESC : T_STRING), open_off, emit);
       } else {
-        tok_put(tz, tok_make(open_off, 0, T_STR_OPEN), emit);
-        tok_put(tz, tok_make(off, 0, has_bs ? T_STR_CLOSE_ESC : T_STR_CLOSE), emit);
+        tok_put(tz, tok_make(open_off, 0, T_STR_OPEN), open_off, emit);
+        tok_put(tz, tok_make(off, 0, has_bs ? T_STR_CLOSE_ESC : T_STR_CLOSE), off, emit);
       }
     } else if (st & bit) {
       const uint32_t c = win_byte(w, k);
@@ -476,9 +484,9 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
         // folds onto the token held back unless that one has its punctuation already, or takes none
         const uint32_t pd = tz.pend;
         if ((pd & TF_MASK) == 0 && !((TOK_NOFOLD >> tok_cls(pd)) & 1u)) tz.pend = pd | (c == ':' ? TF_COLON : TF_COMMA);
-        else tok_put(tz, tok_make(off, 0, c == ':' ? T_COLON : T_COMMA), emit);
+        else tok_put(tz, tok_make(off, 0, c == ':' ? T_COLON : T_COMMA), off, emit);
       } else {
-        tok_put(tz, tok_make(off, 0, ((c & 2u) ? T_OBJ_OPEN : T_OBJ_CLOSE) + ((c & 0x20u) ? 0u : 1u)), emit);
+        tok_put(tz, tok_make(off, 0, ((c & 2u) ? T_OBJ_OPEN : T_OBJ_CLOSE) + ((c & 0x20u) ? 0u : 1u)), off, emit);
       }
     } else {  // a scalar run ends at k
       // its start is in this window (a begin bit at or below k) or carried from an earlier one
@@ -491,7 +499,7 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
       }
       const uint32_t len = off + 1 - start;
       if (len > TOK_MAX_SCALAR) { tz.status = ST_BAD; return; }
-      tok_put(tz, tok_scalar(start, len), emit);
+      tok_put(tz, tok_scalar(start, len), start, emit);
     }
   }
   if (begins) tz.sc_start = uint32_t(lo + int32_t(ctz32(begins)));  // a run that continues
@@ -510,14 +518,15 @@ JL_HD void tokenize_window(const uint8_t* p, uint32_t n, const uint32_t w[4], in
 // Line end: a scalar running to the last byte, then the token held back.
 template <typename Emit>
 JL_HD void tokenize_end(uint32_t n, Tokenizer& tz, Emit&& emit) {
-  if (tz.status == ST_OK && tz.in_str) tok_put(tz, tok_make(tz.str_open, 0, T_STR_OPEN), emit);  // never closed
+  if (tz.status == ST_OK && tz.in_str) tok_put(tz, tok_make(tz.str_open, 0, T_STR_OPEN), tz.str_open, emit);  // never closed
   if (tz.status == ST_OK && tz.sc_carry) {
     const uint32_t len = n - tz.sc_start;
     if (len > TOK_MAX_SCALAR) { tz.status = ST_BAD; return; }
-    tok_put(tz, tok_scalar(tz.sc_start, len), emit);
+    tok_put(tz, tok_scalar(tz.sc_start, len), tz.sc_start, emit);
     tz.sc_carry = 0;
   }
   if (tz.status == ST_OK && tz.pend != TOK_NONE) {
+    tz.out_off = tz.pend_off;
     emit(tz.pend);
     tz.pend = TOK_NONE;
   }
@@ -687,10 +696,11 @@ JL_HD void dfa_str_close(const uint8_t* p, uint32_t off, bool has_bs, Dfa<Genera
   }
 }
 
-// One token's own transition through the JSON grammar and the Action.logSchema extraction.
+// One token's own transition through the JSON grammar and the Action.logSchema extraction. `off` is the
+// token's line offset: tok_off(tok), or the whole offset on a line over TOK_MAX_LINE (General only).
 template <bool General>
-JL_HD void dfa_token_own(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
-  const uint32_t cls = tok_cls(tok), off = tok_off(tok);
+JL_HD void dfa_token_own(const uint8_t* p, uint32_t tok, uint32_t off, Dfa<General>& d) {
+  const uint32_t cls = tok_cls(tok);
   const uint8_t stt = d.state;
   if (cls == T_STRING || cls == T_STRING_ESC) {
     if (dfa_str_open(off, d)) dfa_str_close(p, off + 1 + tok_aux(tok), cls == T_STRING_ESC, d);
@@ -800,14 +810,18 @@ JL_HD void dfa_token_own(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
 // One token: its own transition, then the ':' or ',' folded onto it, checked as the stand-alone
 // T_COLON / T_COMMA is (a ':' needs S_COLON, a ',' needs S_AFTER inside a container).
 template <bool General>
-JL_HD void dfa_token(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
-  dfa_token_own<General>(p, tok, d);
+JL_HD void dfa_token(const uint8_t* p, uint32_t tok, uint32_t off, Dfa<General>& d) {
+  dfa_token_own<General>(p, tok, off, d);
   const uint32_t fl = tok_flags(tok);
   if (fl == 0 || d.status != ST_OK) return;
   const bool colon = (fl & TF_COLON) != 0;
   const bool ok = fl != TF_MASK && (colon ? d.state == S_COLON : (d.state == S_AFTER && d.depth != 0));
   if (!ok) { d.status = ST_BAD; return; }
   d.state = (colon || d.is_arr(d.depth)) ? S_VALUE : S_KEY;
+}
+template <bool General>
+JL_HD void dfa_token(const uint8_t* p, uint32_t tok, Dfa<General>& d) {
+  dfa_token<General>(p, tok, tok_off(tok), d);
 }
 
 template <bool General>
@@ -991,7 +1005,8 @@ JL_HD void parse_line_t(const uint8_t* p, uint32_t n, LineOut& out) {
   const uint32_t o0 = uint32_t(pa & 15);
   const uint32_t nwin = (o0 + n + 15) >> 4;
   auto step = [&](uint32_t t) {
-    if (d.status == ST_OK) dfa_token<General>(p, t, d);
+    // General: the offset that travels beside the token (a line over TOK_MAX_LINE overflows the token's field)
+    if (d.status == ST_OK) dfa_token<General>(p, t, General ? tz.out_off : tok_off(t), d);
   };
   for (uint32_t j = 0; j < nwin && tz.status == ST_OK && d.status == ST_OK; ++j) {
     uint32_t w[4];

@@ -91,6 +91,19 @@ def test_small_segments(engine, corpus):
         _compare(lines, _parse(engine, body))
 
 
+def test_lines_over_the_token_offset_limit(engine):
+    """Lines over 65535 bytes (k_json_hard's General walker): members, null tag values and keys behind offset
+    65535 and behind 2 * 65536, between ordinary lines, in one commit and each in a commit of its own."""
+    from tests.test_json_fold import ADD, REMOVE, over_the_line_limit_cases
+    cases = over_the_line_limit_cases()
+    lines = [ADD]
+    for line in cases:
+        lines += [line, REMOVE, ADD]
+    _compare(lines, _parse(engine, b"".join(l + b"\n" for l in lines)))
+    for line in cases[:9]:
+        _compare([line], _parse(engine, line + b"\n"))
+
+
 def test_both_paths_on_the_bounds_build():
     lib = os.path.join(ROOT, "delta_amd", "libdeltareplay_bounds.so")
     assert os.path.exists(lib), "make builds libdeltareplay_bounds.so"

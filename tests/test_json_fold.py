@@ -473,3 +473,33 @@ def test_misplaced_punctuation_sweep(lib):
     assert stats.get("hard", 0) == 0, stats
     # nearly every misplacement is an error row; the few that are not land inside a string
     assert stats[K_ERROR] > len(cases) // 2 and stats.get(K_ADD, 0) > 0 and stats.get(K_REMOVE, 0) > 0, stats
+
+
+def over_the_line_limit_cases():
+    """Lines over TOK_MAX_LINE (65535 bytes), which only the General walker takes: a token's offset field has 16
+    bits, so every member here lies behind a string that pushes it past offset 65535, or past 2 * 65536 -- the
+    keys the walker must match (path, size, deletionTimestamp), their values, a null among the tags, an escaped
+    path, a scalar the grammar refuses."""
+    out = []
+    for pad in (65525, 65536, 2 * 65536 + 100, 3 * 65536 - 40):
+        s = b'"' + b"s" * pad + b'"'
+        out += [b'{"add":{"stats":' + s + b',"tags":{"u":null}}}',
+                b'{"add":{"stats":' + s + b',"path":"late/p\\u0041th","size":9007199254740993,"tags":{"t":"x","u":null}}}',
+                b'{"add":{"path":"early","stats":' + s + b',"partitionValues":{"p":null},"size":-5,"path":"last wins"}}',
+                b'{"remove":{"tags":{"k":' + s + b'},"path":"r","deletionTimestamp":1700000000001,"size":12}}',
+                b'{"commitInfo":{"x":' + s + b'},"remove":{"path":"r2","deletionTimestamp":null}}',
+                b'{"add":{"stats":' + s + b',"size":1.5}}',
+                b'{"add":{"stats":' + s + b',"tags":{"u":nul}}}',
+                b'{"metaData":{"id":' + s + b',"x":[null,true,false,{"y":null}]}}',
+                b' ' * pad + b'{"add":{"path":"behind blanks","size":3,"tags":{"u":null}}}']
+    return out
+
+
+def test_lines_over_the_token_offset_limit(lib):
+    stats = {}
+    for line in over_the_line_limit_cases():
+        assert len(line) > 65535
+        for align in (0, 7):
+            check(lib, line, align, stats)
+    assert stats["hard"] == 2 * len(over_the_line_limit_cases())      # every one is the General walker's
+    assert stats[K_ADD] and stats[K_REMOVE] and stats[K_ERROR]
