@@ -3802,7 +3802,7 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& given
       for (int32_t u = 0; u < la.nucol; ++u)
         if (la.ucol[u] == f.col) f.slot = u;
       f.ctype = leaf_kind(la.cols[f.col].type);
-      la.extended |= f.ctype == DR_T_FLOAT || f.ctype == DR_T_DOUBLE || f.ctype == DR_T_DECIMAL || is_pattern_op(f.op);
+      la.extended |= f.ctype == DR_T_FLOAT || f.ctype == DR_T_DOUBLE || f.ctype == DR_T_DECIMAL || is_pattern_op(f.op) || f.nfn > 0;
     }
     const uint64_t ng = filter_leaf_groups(st.n_live);
     DBuf<uint64_t> mask(ctx, uint64_t(filter_leaf_mask_words()) * ng), wg_off(ctx, ng + 1);

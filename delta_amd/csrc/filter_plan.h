@@ -12,6 +12,7 @@ constexpr int PV_STACK = 32;  // k_filter_typed's value stack (lowered program)
 constexpr int FL_MAXPROG = 128, FL_MAXLEAF = 64, FL_MAXI64 = 1024, FL_MAXSTR = 256;
 constexpr uint32_t FD_MAXTAB = 32768;
 constexpr int FL_UCOLS = 4;   // distinct columns a leaf program preloads per tile
+constexpr int FL_MAXFN = 4;   // date functions a leaf applies to its column (a longer chain: k_filter_typed)
 
 // Floating-point order keys (SQLOrderingUtil.compareDoubles / compareFloats: -0.0 = 0.0, NaN = NaN,
 // NaN above +Infinity): the bits with every NaN canonical and -0.0 turned into +0.0, then the magnitude
@@ -68,7 +69,8 @@ DR_HD inline int32_t leaf_kind(int32_t type) {
 }
 
 // Leaf form of a predicate (pred_plan.cpp leafify): every leaf compares one partition column with
-// literals -- col op lit, col IN (lits), col IS [NOT] NULL -- and AND / OR / NOT combine their
+// literals -- col op lit, col IN (lits), col IS [NOT] NULL, the column possibly under a chain of date
+// functions -- and AND / OR / NOT combine their
 // three-valued results on a 2-bit-per-entry stack held in one register.
 struct FilterLeaf {
   int32_t col;       // predicate column
@@ -81,6 +83,11 @@ struct FilterLeaf {
                      // against DOUBLE literals: 2 = widen the value's key (fp_key_widen) first
   int32_t slot;      // k_filter_leaf: the preloaded column slot holding `col` (-1: loaded per leaf)
   int32_t ctype;     // leaf_kind of the column's dr_pred_type
+  // a function leaf, f(col) op literals: the date functions (date_fn.h) applied to the column's value,
+  // innermost first, before the comparison; the literal slots then hold plain integers. An aggregate
+  // initialiser that stops before these reads as "no function".
+  int32_t nfn;               // 0 .. FL_MAXFN
+  int32_t fn[FL_MAXFN], farg[FL_MAXFN];  // DR_OP_YEAR .. DR_OP_TRUNC_DATE and the op's arg
 };
 enum : int32_t { LEAF_OP_LEAF = 0, LEAF_OP_AND = 1, LEAF_OP_OR = 2, LEAF_OP_NOT = 3 };
 // device-only opcodes of the lowered program (pred_plan.cpp lower_program): an IN list is folded

@@ -12,9 +12,12 @@
 // (include/deltareplay.h, dr_pred_op) over the typed columns.
 #include "dev_common.h"
 #include "kernels.h"
+#include "date_fn.h"
 #include "like_lane.h"
 #include "../../include/deltareplay.h"
 #include <hipcub/device/device_merge_sort.hpp>
+#include <cstddef>
+#include <type_traits>
 
 namespace dr {
 namespace dev {
@@ -843,6 +846,14 @@ __global__ void __launch_bounds__(256) k_filter_typed(FilterTypedArgs a) {
         if (!x.null) x.v = !x.v;
         break;
       }
+      // the date functions (date_fn.h): NULL stays NULL; the host has checked the operand's type
+      case DR_OP_YEAR: case DR_OP_QUARTER: case DR_OP_MONTH: case DR_OP_DAYOFMONTH: case DR_OP_DAYOFWEEK:
+      case DR_OP_DAYOFYEAR: case DR_OP_WEEKOFYEAR: case DR_OP_TO_DATE: case DR_OP_DATE_ADD: case DR_OP_TRUNC_DATE: {
+        SV& x = st[sp - 1];
+        if (!x.null) x.v = df::date_fn(op, arg, x.v);
+        x.str = SV_INT;
+        break;
+      }
       default: bad = true;
     }
   }
@@ -875,13 +886,15 @@ constexpr uint32_t FL_FILES = FL_T * FL_PER;  // files per tile (4 FL_PER mask w
 // The leaf result from a column value already in registers (nul, v = integer or big-endian 8-byte
 // string prefix, vn = string length); the long-string gather reads the column by file ordinal i.
 // The literals are the workgroup's LDS copies (li: integers and IN sets, ls8 / lso: the string
-// literals' prefixes and offsets). X: the leaf may be of a FLOAT / DOUBLE / DECIMAL column or a
-// string pattern (the kernels for the older types and ops are instantiated without that code:
-// k_filter_leaf is register-tuned).
+// literals' prefixes and offsets). X: the leaf may be of a FLOAT / DOUBLE / DECIMAL column, a
+// string pattern or a function leaf (the kernels for the older types and ops are instantiated without
+// that code: k_filter_leaf is register-tuned). A function leaf's chain (L.nfn functions) is read from
+// `chain`, the leaf where it lies in LDS or global memory, so that no copy of it is indexed in registers.
 template <bool X>
 __device__ __forceinline__ uint32_t leaf_value(const uint8_t* lit_str, const FilterLeaf& L, const PvColumn& col,
                                                uint64_t i, uint32_t nul, int64_t v, uint32_t vn, const int64_t* li,
-                                               const uint64_t* ls8, const uint64_t* lso, const int64_t* lhi) {
+                                               const uint64_t* ls8, const uint64_t* lso, const int64_t* lhi,
+                                               const FilterLeaf* chain = nullptr) {
   const bool str = L.ctype == DR_T_STRING, dec = X && L.ctype == DR_T_DECIMAL;
   const bool vnull = nul != 0;
   if (L.op == DR_OP_ISNULL) return vnull ? 1u : 0u;
@@ -889,6 +902,9 @@ __device__ __forceinline__ uint32_t leaf_value(const uint8_t* lit_str, const Fil
   if (L.op == DR_OP_NSEQ && (vnull || L.lit_null)) return (vnull && L.lit_null) ? 1u : 0u;
   if (L.op != DR_OP_IN && L.lit_null) return 2u;
   if (vnull) return 2u;
+  if (X) {  // uniform: a function leaf compares f(v); every function is total, so v's null tests stand
+    for (int32_t q = 0; q < L.nfn; ++q) v = df::date_fn(chain->fn[q], chain->farg[q], v);
+  }
   if (X && L.pad == 2) v = fp_key_widen(v);  // uniform: a FLOAT column against DOUBLE literals
   // a decimal's high word: loaded here, for decimal leaves only and non-NULL values only (a NULL
   // stands for the files past the end of a partial tile too), lhi[] read from global memory
@@ -992,6 +1008,16 @@ __device__ __forceinline__ void load_col4(const FilterLeafArgs& a, const PvColum
   }
 }
 
+// What k_filter_leaf and k_filter_dict stage of a leaf in LDS: the fields before the function chain,
+// the whole leaf as it was before there were function leaves. Only k_filter_leaf_x stages the chain.
+struct FilterLeafHead {
+  int32_t col, op, lit, nlit, lit_null, pad, slot, ctype;
+};
+static_assert(offsetof(FilterLeaf, nfn) == sizeof(FilterLeafHead) && offsetof(FilterLeaf, ctype) == offsetof(FilterLeafHead, ctype),
+              "FilterLeafHead is the beginning of FilterLeaf");
+__device__ __forceinline__ const FilterLeaf* leaf_chain(const FilterLeaf& f) { return &f; }
+__device__ __forceinline__ const FilterLeaf* leaf_chain(const FilterLeafHead&) { return nullptr; }
+
 // Persistent workgroups (grid-stride over tiles of FL_FILES files). The program, its leaves and
 // every literal are copied to LDS once per workgroup, and the leaf fields are read as wave-uniform
 // (scalar) values, so a tile issues no load but its column values: r04's first persistent build read
@@ -1003,12 +1029,13 @@ __device__ __forceinline__ void load_col4(const FilterLeafArgs& a, const PvColum
 // count: no barrier per tile.
 template <bool X>
 __device__ __forceinline__ void filter_leaf_tiles(const FilterLeafArgs& a) {
+  using StagedLeaf = typename std::conditional<X, FilterLeaf, FilterLeafHead>::type;
   __shared__ int32_t sprog[2 * FL_MAXPROG];
-  __shared__ FilterLeaf sleaf[FL_MAXLEAF];
+  __shared__ StagedLeaf sleaf[FL_MAXLEAF];
   __shared__ int64_t slit[FL_MAXI64];
   __shared__ uint64_t ss8[FL_MAXSTR + 1], ssoff[FL_MAXSTR + 1];
   for (int k = threadIdx.x; k < 2 * a.nprog; k += FL_T) sprog[k] = a.prog[k];
-  for (int k = threadIdx.x; k < a.nleaves; k += FL_T) sleaf[k] = a.leaves[k];
+  for (int k = threadIdx.x; k < a.nleaves; k += FL_T) sleaf[k] = *reinterpret_cast<const StagedLeaf*>(&a.leaves[k]);
   for (int k = threadIdx.x; k < a.n_i64; k += FL_T) slit[k] = a.lit_i64[k];
   for (int k = threadIdx.x; k <= a.n_str; k += FL_T) {
     ss8[k] = a.lit_s8[k];
@@ -1046,6 +1073,7 @@ __device__ __forceinline__ void filter_leaf_tiles(const FilterLeafArgs& a) {
         L.pad = __builtin_amdgcn_readfirstlane(sleaf[li].pad);
         L.slot = __builtin_amdgcn_readfirstlane(sleaf[li].slot);
         L.ctype = __builtin_amdgcn_readfirstlane(sleaf[li].ctype);
+        if constexpr (X) L.nfn = __builtin_amdgcn_readfirstlane(sleaf[li].nfn);
         const PvColumn& col = a.cols[L.col];  // read only by the long-string gather
         uint32_t n0[FL_PER], l0[FL_PER];
         int64_t v0[FL_PER];
@@ -1066,7 +1094,7 @@ __device__ __forceinline__ void filter_leaf_tiles(const FilterLeafArgs& a) {
         for (int j = 0; j < FL_PER; ++j)
           stk[j] = (stk[j] << 2) |
                    leaf_value<X>(a.lit_str, L, col, base + threadIdx.x + uint64_t(j) * FL_T, n0[j], v0[j], l0[j], slit, ss8, ssoff,
-                              a.lit_hi);
+                              a.lit_hi, leaf_chain(sleaf[li]));
       } else if (op == LEAF_OP_NOT) {
 #pragma unroll
         for (int j = 0; j < FL_PER; ++j) {
@@ -1097,8 +1125,8 @@ __device__ __forceinline__ void filter_leaf_tiles(const FilterLeafArgs& a) {
 }
 // k_filter_leaf: programs over STRING / BINARY, the integer kinds, DATE, BOOLEAN and TIMESTAMP
 // columns, exactly the code it was before the other types; k_filter_leaf_x: programs with a leaf
-// over a FLOAT, DOUBLE or DECIMAL column or a string pattern leaf (FilterLeafArgs::extended, set by
-// the host).
+// over a FLOAT, DOUBLE or DECIMAL column, a string pattern leaf or a function leaf
+// (FilterLeafArgs::extended, set by the host).
 __global__ void __launch_bounds__(FL_T) k_filter_leaf(FilterLeafArgs a) { filter_leaf_tiles<false>(a); }
 __global__ void __launch_bounds__(FL_T) k_filter_leaf_x(FilterLeafArgs a) { filter_leaf_tiles<true>(a); }
 
@@ -1227,7 +1255,7 @@ __global__ void __launch_bounds__(256) k_dict_leaf(DictLeafArgs a, uint32_t tota
   if (t >= total) return;
   int32_t l = 0;
   while (l + 1 < a.nleaves && a.tab_off[l + 1] <= t) ++l;
-  const FilterLeaf L = a.leaves[l];
+  const FilterLeaf& L = a.leaves[l];
   const uint32_t k = t - a.tab_off[l];
   const PvColumn& col = a.cols[L.col];
   uint32_t nul = 1, vn = 0;
@@ -1245,18 +1273,18 @@ __global__ void __launch_bounds__(256) k_dict_leaf(DictLeafArgs a, uint32_t tota
   }
   // X = true whatever the column: one thread per (leaf, code) has no register budget to keep, and a
   // decimal(p <= 18) leaf reads w64hi[row] (allocated for every decimal; row is a live file) and lit_hi
-  a.tab[t] = uint8_t(leaf_value<true>(a.lit_str, L, col, row, nul, v, vn, a.lit_i64, a.lit_s8, a.lit_str_off, a.lit_hi));
+  a.tab[t] = uint8_t(leaf_value<true>(a.lit_str, L, col, row, nul, v, vn, a.lit_i64, a.lit_s8, a.lit_str_off, a.lit_hi, &L));
 }
 
 // The per-file pass over codes: tiles of FL_FILES files, FL_PER per lane; every leaf is one LDS
 // byte read per file.
 __global__ void __launch_bounds__(FL_T) k_filter_dict(FilterDictArgs a) {
   __shared__ int32_t sprog[2 * FL_MAXPROG];
-  __shared__ FilterLeaf sleaf[FL_MAXLEAF];
+  __shared__ FilterLeafHead sleaf[FL_MAXLEAF];
   __shared__ uint32_t stoff[FL_MAXLEAF + 1];
   __shared__ uint8_t stab[FD_MAXTAB];
   for (int k = threadIdx.x; k < 2 * a.nprog; k += FL_T) sprog[k] = a.prog[k];
-  for (int k = threadIdx.x; k < a.nleaves; k += FL_T) sleaf[k] = a.leaves[k];
+  for (int k = threadIdx.x; k < a.nleaves; k += FL_T) sleaf[k] = *reinterpret_cast<const FilterLeafHead*>(&a.leaves[k]);
   for (int k = threadIdx.x; k <= a.nleaves; k += FL_T) stoff[k] = a.tab_off[k];
   for (uint32_t k = threadIdx.x; k < a.tab_bytes; k += FL_T) stab[k] = a.tab[k];
   __syncthreads();

@@ -528,7 +528,7 @@ struct FilterLeafArgs {
   int32_t nucol;                 // distinct columns the leaves read (0: more than FL_UCOLS, loaded per leaf)
   int32_t ucol[4];               // FL_UCOLS: those columns (predicate column indices)
   const int64_t* lit_hi;         // [n_i64] DECIMAL literals' high words (read by decimal leaves only)
-  int32_t extended;              // a leaf reads a FLOAT / DOUBLE / DECIMAL column or is a string pattern: k_filter_leaf_x
+  int32_t extended;              // a leaf reads a FLOAT / DOUBLE / DECIMAL column, is a string pattern or applies date functions: k_filter_leaf_x
 };
 // 1024-file tiles of k_filter_leaf: the sizes of `mask` (x16) and `wg_count`
 uint64_t filter_leaf_groups(uint64_t n_live);

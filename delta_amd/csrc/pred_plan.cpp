@@ -6,6 +6,7 @@
 #include <functional>
 #include <utility>
 
+#include "date_fn.h"
 #include "like_lane.h"
 
 namespace dr {
@@ -114,6 +115,57 @@ bool compile_patterns(const dr_predicate& p, PatternPred& out) {
   return true;
 }
 
+// ---- date functions (DR_OP_YEAR .. DR_OP_TRUNC_DATE) -------------------------------------------------
+static_assert(int(df::FN_YEAR) == int(DR_OP_YEAR) && int(df::FN_QUARTER) == int(DR_OP_QUARTER) && int(df::FN_MONTH) == int(DR_OP_MONTH) &&
+              int(df::FN_DAYOFMONTH) == int(DR_OP_DAYOFMONTH) && int(df::FN_DAYOFWEEK) == int(DR_OP_DAYOFWEEK) &&
+              int(df::FN_DAYOFYEAR) == int(DR_OP_DAYOFYEAR) && int(df::FN_WEEKOFYEAR) == int(DR_OP_WEEKOFYEAR) && int(df::FN_TO_DATE) == int(DR_OP_TO_DATE) &&
+              int(df::FN_DATE_ADD) == int(DR_OP_DATE_ADD) && int(df::FN_TRUNC_DATE) == int(DR_OP_TRUNC_DATE),
+              "date_fn.h's function codes are the ABI's opcodes");
+static const char* date_fn_name(int op) {
+  static const char* const names[] = {"YEAR", "QUARTER", "MONTH", "DAYOFMONTH", "DAYOFWEEK", "DAYOFYEAR", "WEEKOFYEAR",
+                                      "TO_DATE", "DATE_ADD", "TRUNC_DATE"};
+  return names[op - DR_OP_YEAR];
+}
+static int32_t date_fn_operand(int op) { return op == DR_OP_TO_DATE ? DR_T_TIMESTAMP : DR_T_DATE; }
+static int32_t date_fn_result(int op) { return op >= DR_OP_TO_DATE ? DR_T_DATE : DR_T_INT; }
+static const char* type_name(int32_t t) { return t == DR_T_TIMESTAMP ? "TIMESTAMP" : t == DR_T_DATE ? "DATE" : "INT"; }
+static bool int_kind(int32_t t) { return t >= DR_T_BYTE && t <= DR_T_LONG; }
+// The static type of op k's value where the date rules need one: a column's, a literal's, a function's
+// result; -1 for anything else (a boolean).
+static int32_t value_type(const dr_predicate& p, int32_t k) {
+  const int op = p.ops[k].opcode, arg = p.ops[k].arg;
+  return op == DR_OP_COL ? p.col_types[arg] : op == DR_OP_LIT ? p.lit_types[arg] : is_date_fn(op) ? date_fn_result(op) : -1;
+}
+// Function op k over the operand rooted at op vk: a column or a function of the operand type, then the arg.
+static void check_date_fn(const dr_predicate& p, int32_t k, int32_t vk) {
+  const int op = p.ops[k].opcode, arg = p.ops[k].arg, vop = p.ops[vk].opcode;
+  const int32_t want = date_fn_operand(op);
+  if ((vop != DR_OP_COL && !is_date_fn(vop)) || value_type(p, vk) != want)
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the operand must be a %s value, found %s", k, date_fn_name(op),
+                               type_name(want), pred_op_text(p, vk).c_str()));
+  if (op == DR_OP_TRUNC_DATE && (arg < 0 || arg > 3))
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (TRUNC_DATE): the unit (arg %d) must be 0 YEAR, 1 QUARTER, 2 MONTH or 3 WEEK", k, arg));
+  if (op != DR_OP_TRUNC_DATE && op != DR_OP_DATE_ADD && arg != 0)
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): takes no argument (arg %d must be 0)", k, date_fn_name(op), arg));
+}
+// Function result fk (op k compares it) against the value rooted at op ok: a literal of the result's kind
+// or NULL; a column or another function result of the same family (integer kinds, or DATE).
+static void check_date_fn_peer(const dr_predicate& p, int32_t k, int32_t fk, int32_t ok) {
+  const int fop = p.ops[fk].opcode;
+  const int32_t rt = date_fn_result(fop), ot = value_type(p, ok);
+  auto same_family = [&](int32_t t) { return rt == DR_T_DATE ? t == DR_T_DATE : int_kind(t); };
+  if (p.ops[ok].opcode == DR_OP_LIT) {
+    const int32_t l = p.ops[ok].arg;
+    if (!p.lit_null[l] && !same_family(ot))
+      fail(DR_E_INVALID_ARG, fmt("predicate literal %d (type %d) does not fit the result of op %d (%s, type %d)", l, ot, fk,
+                                 date_fn_name(fop), rt));
+    return;
+  }
+  if (!same_family(ot))
+    fail(DR_E_INVALID_ARG, fmt("predicate op %d: the result of op %d (%s, type %d) does not compare with %s", k, fk,
+                               date_fn_name(fop), rt, pred_op_text(p, ok).c_str()));
+}
+
 // ---- the program as a tree ---------------------------------------------------------------------------
 // The values an op takes off the stack, every opcode listed; -1: no such opcode, or an IN list of a
 // negative length.
@@ -122,6 +174,8 @@ static int64_t arity(const dr_pred_op& o) {
     case DR_OP_COL: case DR_OP_LIT:
       return 0;
     case DR_OP_ISNULL: case DR_OP_ISNOTNULL: case DR_OP_NOT:
+    case DR_OP_YEAR: case DR_OP_QUARTER: case DR_OP_MONTH: case DR_OP_DAYOFMONTH: case DR_OP_DAYOFWEEK:
+    case DR_OP_DAYOFYEAR: case DR_OP_WEEKOFYEAR: case DR_OP_TO_DATE: case DR_OP_DATE_ADD: case DR_OP_TRUNC_DATE:
       return 1;
     case DR_OP_EQ: case DR_OP_NE: case DR_OP_LT: case DR_OP_LE: case DR_OP_GT: case DR_OP_GE: case DR_OP_NSEQ:
     case DR_OP_AND: case DR_OP_OR:
@@ -226,14 +280,36 @@ void check_program(const dr_predicate& p) {
                              : arity(p.ops[k]) < 0 ? fmt("unknown predicate opcode %d", op) : "predicate stack underflow");
     const Kids ch = t.kids(k);
     if (is_pattern_op(op)) check_pattern_op(p, k, ch[0], ch[1]);
+    if (is_date_fn(op)) check_date_fn(p, k, ch[0]);
+    // an INT or a DATE is no boolean: a function result goes under a comparison, IN, IS [NOT] NULL or
+    // another function, not under AND / OR / NOT
+    if (op == DR_OP_AND || op == DR_OP_OR || op == DR_OP_NOT)
+      for (size_t q = 0; q < ch.n; ++q)
+        if (is_date_fn(p.ops[ch[q]].opcode))
+          fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the operand must be a boolean, found the result of op %d (%s, type %d)", k,
+                                     op == DR_OP_AND ? "AND" : op == DR_OP_OR ? "OR" : "NOT", ch[q],
+                                     date_fn_name(p.ops[ch[q]].opcode), date_fn_result(p.ops[ch[q]].opcode)));
+    // a function result on either side of a comparison, or as the value or an element of an IN
+    auto peers = [&](int32_t ak, int32_t bk) {
+      if (is_date_fn(p.ops[ak].opcode)) check_date_fn_peer(p, k, ak, bk);
+      else if (is_date_fn(p.ops[bk].opcode)) check_date_fn_peer(p, k, bk, ak);
+    };
     if (op >= DR_OP_EQ && op <= DR_OP_NSEQ) {
       fits(ch[0], ch[1]);
       fits(ch[1], ch[0]);
+      peers(ch[0], ch[1]);
     } else if (op == DR_OP_IN) {
-      for (size_t q = 1; q < ch.n; ++q) fits(ch[0], ch[q]);
+      for (size_t q = 1; q < ch.n; ++q) {
+        fits(ch[0], ch[q]);
+        peers(ch[0], ch[q]);
+      }
     }
   }
   if (t.left != 1) fail(DR_E_INVALID_ARG, "predicate program must leave one value");
+  const int last = p.ops[p.nops - 1].opcode;  // nor is one the program's value
+  if (is_date_fn(last))
+    fail(DR_E_INVALID_ARG, fmt("predicate program must leave a boolean, op %d (%s) leaves a value of type %d", p.nops - 1,
+                               date_fn_name(last), date_fn_result(last)));
 }
 
 std::vector<int32_t> lower_program(const dr_predicate& p) {
@@ -270,6 +346,20 @@ std::vector<int32_t> lower_program(const dr_predicate& p) {
 bool leafify(const dr_predicate& p, LeafPlan& L) {
   const Tree t = tree_of(p);
   auto is_col = [&](int32_t k) { return p.ops[k].opcode == DR_OP_COL; };
+  // chain(col): a column under at most FL_MAXFN date functions (none: the bare column); `f` gets the
+  // column and the functions, innermost first
+  auto is_chain = [&](int32_t k, FilterLeaf& f) {
+    int32_t n = 0;
+    for (int32_t q = k; is_date_fn(p.ops[q].opcode); q = t.kids(q)[0]) ++n;
+    if (n > FL_MAXFN) return false;
+    f.nfn = n;
+    for (; is_date_fn(p.ops[k].opcode); k = t.kids(k)[0]) {
+      f.fn[--n] = p.ops[k].opcode;
+      f.farg[n] = p.ops[k].arg;
+    }
+    f.col = p.ops[k].arg;
+    return is_col(k);
+  };
   auto is_lit = [&](int32_t k) { return p.ops[k].opcode == DR_OP_LIT; };
   auto is_str = [](int32_t t) { return leaf_kind(t) == DR_T_STRING; };
   // string (and binary) columns with literals of bytes, others numeric; the new types by lit_fits
@@ -317,23 +407,33 @@ bool leafify(const dr_predicate& p, LeafPlan& L) {
         L.prog.push_back(LEAF_OP_NOT);
         L.prog.push_back(0);
         return true;
-      case DR_OP_ISNULL: case DR_OP_ISNOTNULL:
-        if (!is_col(ch[0])) return false;
-        return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, 0, 0, 0, 0});
+      case DR_OP_ISNULL: case DR_OP_ISNOTNULL: {
+        FilterLeaf f{};
+        if (!is_chain(ch[0], f)) return false;
+        f.op = op;
+        return push_leaf(f);
+      }
       case DR_OP_EQ: case DR_OP_NE: case DR_OP_LT: case DR_OP_LE: case DR_OP_GT: case DR_OP_GE: case DR_OP_NSEQ: {
-        int32_t c, l, fop = op;
-        if (is_col(ch[0]) && is_lit(ch[1])) {
-          c = p.ops[ch[0]].arg; l = p.ops[ch[1]].arg;
-        } else if (is_lit(ch[0]) && is_col(ch[1])) {
-          c = p.ops[ch[1]].arg; l = p.ops[ch[0]].arg;
-          fop = op == DR_OP_LT ? DR_OP_GT : op == DR_OP_GT ? DR_OP_LT : op == DR_OP_LE ? DR_OP_GE
-              : op == DR_OP_GE ? DR_OP_LE : op;
+        FilterLeaf f{};
+        int32_t l;
+        f.op = op;
+        if (is_lit(ch[1]) && is_chain(ch[0], f)) {
+          l = p.ops[ch[1]].arg;
+        } else if (is_lit(ch[0]) && is_chain(ch[1], f)) {
+          l = p.ops[ch[0]].arg;
+          f.op = op == DR_OP_LT ? DR_OP_GT : op == DR_OP_GT ? DR_OP_LT : op == DR_OP_LE ? DR_OP_GE
+               : op == DR_OP_GE ? DR_OP_LE : op;
         } else {
           return false;
         }
-        if (!p.lit_null[l] && !kind_ok(c, l)) return false;
-        const bool widen = !p.lit_null[l] && p.col_types[c] == DR_T_FLOAT && p.lit_types[l] == DR_T_DOUBLE;
-        return push_leaf(FilterLeaf{c, fop, slot(l), 0, p.lit_null[l] ? 1 : 0, widen ? 2 : 0});
+        const int32_t c = f.col;
+        // a function result: an integer against an integer literal, whatever the column (check_program)
+        if (!f.nfn && !p.lit_null[l] && !kind_ok(c, l)) return false;
+        const bool widen = !f.nfn && !p.lit_null[l] && p.col_types[c] == DR_T_FLOAT && p.lit_types[l] == DR_T_DOUBLE;
+        f.lit = slot(l);
+        f.lit_null = p.lit_null[l] ? 1 : 0;
+        f.pad = widen ? 2 : 0;
+        return push_leaf(f);
       }
       case DR_OP_STARTSWITH: case DR_OP_ENDSWITH: case DR_OP_CONTAINS: case DR_OP_LIKE: {
         // check_program: a STRING column and a STRING or NULL literal (LIKE: compiled, compile_patterns)
@@ -347,22 +447,25 @@ bool leafify(const dr_predicate& p, LeafPlan& L) {
         return push_leaf(FilterLeaf{p.ops[ch[0]].arg, op, slot(l), 0, 0, 0});
       }
       case DR_OP_IN: {
-        if (!is_col(ch[0])) return false;
-        const int32_t c = p.ops[ch[0]].arg;
-        const int kind = leaf_kind(p.col_types[c]);
+        FilterLeaf f{};
+        if (!is_chain(ch[0], f)) return false;
+        f.op = DR_OP_IN;
+        const int32_t c = f.col;
+        // a function result is a 32-bit integer: a sorted set or a bitmap, like an INT column's
+        const int kind = f.nfn ? DR_T_INT : leaf_kind(p.col_types[c]);
         const bool str = kind == DR_T_STRING;
         bool has_null = false, widen = false;
         std::vector<int64_t> iv;
         std::vector<std::pair<int64_t, uint64_t>> dv;  // decimals: (high signed, low unsigned)
         std::vector<std::string> sv;
         for (size_t q = 1; q < ch.n; ++q)  // a FLOAT column with a DOUBLE element: all in binary64
-          widen |= is_lit(ch[q]) && !p.lit_null[p.ops[ch[q]].arg] && p.col_types[c] == DR_T_FLOAT &&
+          widen |= !f.nfn && is_lit(ch[q]) && !p.lit_null[p.ops[ch[q]].arg] && p.col_types[c] == DR_T_FLOAT &&
                    p.lit_types[p.ops[ch[q]].arg] == DR_T_DOUBLE;
         for (size_t q = 1; q < ch.n; ++q) {
           if (!is_lit(ch[q])) return false;
           const int32_t l = p.ops[ch[q]].arg;
           if (p.lit_null[l]) { has_null = true; continue; }
-          if (!kind_ok(c, l)) return false;
+          if (!f.nfn && !kind_ok(c, l)) return false;
           if (str) {
             sv.emplace_back(reinterpret_cast<const char*>(p.lit_str_bytes) + p.lit_str_off[l],
                             size_t(p.lit_str_off[l + 1] - p.lit_str_off[l]));
@@ -383,7 +486,10 @@ bool leafify(const dr_predicate& p, LeafPlan& L) {
             L.i64hi.push_back(d.first);
             L.str.emplace_back();
           }
-          return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(dv.size()), has_null ? 1 : 0, 0});
+          f.lit = first;
+          f.nlit = int32_t(dv.size());
+          f.lit_null = has_null ? 1 : 0;
+          return push_leaf(f);
         }
         std::sort(iv.begin(), iv.end());
         iv.erase(std::unique(iv.begin(), iv.end()), iv.end());
@@ -406,14 +512,22 @@ bool leafify(const dr_predicate& p, LeafPlan& L) {
           for (uint64_t w : bits) L.i64.push_back(int64_t(w));
           L.i64hi.resize(L.i64.size(), 0);
           L.str.resize(L.i64.size());
-          return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, 1});
+          f.lit = first;
+          f.nlit = int32_t(m);
+          f.lit_null = has_null ? 1 : 0;
+          f.pad = 1;
+          return push_leaf(f);
         }
         for (size_t q = 0; q < m; ++q) {
           L.i64.push_back(str ? 0 : iv[q]);
           L.i64hi.push_back(0);
           L.str.push_back(str ? sv[q] : std::string());
         }
-        return push_leaf(FilterLeaf{c, DR_OP_IN, first, int32_t(m), has_null ? 1 : 0, widen ? 2 : 0});
+        f.lit = first;
+        f.nlit = int32_t(m);
+        f.lit_null = has_null ? 1 : 0;
+        f.pad = widen ? 2 : 0;
+        return push_leaf(f);
       }
       default:
         return false;

@@ -12,6 +12,7 @@
 namespace dr {
 
 inline bool is_pattern_op(int op) { return op >= DR_OP_STARTSWITH && op <= DR_OP_LIKE; }
+inline bool is_date_fn(int op) { return op >= DR_OP_YEAR && op <= DR_OP_TRUNC_DATE; }
 
 // Host validation of the postfix program: types, literals, operand indices and stack discipline.
 // The only function here that accepts an unchecked program; the others take one it has passed.
@@ -42,8 +43,8 @@ bool compile_patterns(const dr_predicate& p, PatternPred& out);
 // program still needs more than the device stack.
 std::vector<int32_t> lower_program(const dr_predicate& p);
 
-// Leaf form of a program (k_filter_leaf) when every comparison is between one partition column and
-// literals of its kind and the rest is AND / OR / NOT: each leaf is evaluated straight from the typed
+// Leaf form of a program (k_filter_leaf) when every comparison is between one partition column, bare
+// or under at most FL_MAXFN date functions, and literals of its kind and the rest is AND / OR / NOT: each leaf is evaluated straight from the typed
 // K5 cache, IN lists become sorted sets searched by bisection, and the boolean combination runs on
 // a register stack. Returns false (generic interpreter, k_filter_typed) for anything else.
 struct LeafPlan {

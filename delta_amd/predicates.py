@@ -14,7 +14,13 @@ Expressions are nested tuples (the oracle's format): ("col", name), ("lit", type
 ("and", a, b), ("or", a, b), ("not", a), and the string patterns ("startswith", col, lit),
 ("endswith", col, lit), ("contains", col, lit), ("like", col, lit[, escape]) -- Catalyst's StartsWith /
 EndsWith / Contains / Like over a string partition column and a string (or NULL) literal; the escape
-is one character, Spark's default "\\". Types: "string", "byte", "short", "integer", "long",
+is one character, Spark's default "\\". The date functions: ("year", e), ("quarter", e), ("month", e),
+("dayofmonth", e), ("dayofweek", e), ("dayofyear", e), ("weekofyear", e) over a date, ("to_date", e)
+over a timestamp (Cast(ts AS date), session zone UTC), ("date_add", e, n) / ("date_sub", e, n) with n
+an int in the int32 range (no expression) and ("trunc", e, fmt) with fmt one of YEAR | YYYY | YY,
+QUARTER, MONTH | MM | MON, WEEK in any case -- Catalyst's Year .. WeekOfYear, DateAdd / DateSub and
+TruncDate; e is a partition column of the operand's type or another of these functions, so they nest,
+and the result compares with integer literals (year .. weekofyear) or date literals. Types: "string", "byte", "short", "integer", "long",
 "date", "boolean", "float", "double", "timestamp", "binary", "decimal(p,s)" ("decimal" is
 decimal(10,0)). The program is evaluated on the GPU; nothing here evaluates it.
 
@@ -57,6 +63,12 @@ OP_CODE = {"=": 2, "!=": 3, "<": 4, "<=": 5, ">": 6, ">=": 7, "<=>": 8, "in": 9,
            "isnotnull": 11, "and": 12, "or": 13, "not": 14,
            "startswith": 15, "endswith": 16, "contains": 17, "like": 18}
 PATTERN_OPS = ("startswith", "endswith", "contains", "like")
+# the date functions: DR_OP_YEAR .. DR_OP_TRUNC_DATE ("date_sub" is DATE_ADD of -n)
+DATE_FN_CODE = {"year": 19, "quarter": 20, "month": 21, "dayofmonth": 22, "dayofweek": 23, "dayofyear": 24,
+                "weekofyear": 25, "to_date": 26, "date_add": 27, "date_sub": 27, "trunc": 28}
+DATE_FN_ARG_OPS = ("date_add", "date_sub", "trunc")  # a third element that is no expression
+TRUNC_UNIT = {"year": 0, "yyyy": 0, "yy": 0, "quarter": 1, "month": 2, "mm": 2, "mon": 2, "week": 3}
+_INT_TYPES = ("byte", "short", "integer", "long")
 _EPOCH = _dt.date(1970, 1, 1)
 
 
@@ -83,6 +95,8 @@ def _refs(expr) -> List[str]:
         return _refs(expr[1]) + [r for l in expr[2] for r in _refs(l)]
     if op == "like":  # a fourth element is the escape character, no expression
         return _refs(expr[1]) + _refs(expr[2])
+    if op in DATE_FN_ARG_OPS:  # the day count / the format is no expression either
+        return _refs(expr[1])
     return [r for a in expr[1:] for r in _refs(a)]
 
 
@@ -509,6 +523,68 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
         emit(pat)
         p.ops.append((OP_CODE[op], arg))
 
+    def value_type(e):
+        """The type name of a column, a literal or a date function's result; None for anything else."""
+        if e[0] == "col":
+            exact = _resolve(e[1], parts)
+            return schema[exact] if exact is not None else None
+        if e[0] == "lit":
+            return e[1]
+        if e[0] in DATE_FN_CODE:
+            return "integer" if DATE_FN_CODE[e[0]] < DATE_FN_CODE["to_date"] else "date"
+        return None
+
+    def date_fn(e):
+        """A date function: the operand a column or another function of the operand's type."""
+        op = e[0]
+        if len(e) != (3 if op in DATE_FN_ARG_OPS else 2):
+            raise PredicateError("%s takes %s" % (op, "an expression and a format" if op == "trunc" else
+                                                  "an expression and a day count" if op in DATE_FN_ARG_OPS else "one expression"))
+        want = "timestamp" if op == "to_date" else "date"
+        x = e[1]
+        if not isinstance(x, tuple) or (x[0] != "col" and x[0] not in DATE_FN_CODE):
+            raise PredicateError("%s: the operand must be a %s partition column or date function, found %r"
+                                 % (op, want, x[0] if isinstance(x, tuple) else x))
+        if x[0] == "col" and _resolve(x[1], parts) is None:
+            col(x[1])  # raises: no partition column
+        if value_type(x) != want:
+            raise PredicateError("%s: the operand must be a %s value, found %s of type %s"
+                                 % (op, want, "column %s" % x[1] if x[0] == "col" else x[0], value_type(x)))
+        arg = 0
+        if op == "trunc":
+            if not isinstance(e[2], str) or e[2].lower() not in TRUNC_UNIT:
+                raise PredicateError("trunc: the format must be one of YEAR, YYYY, YY, QUARTER, MONTH, MM, MON, WEEK, got %r"
+                                     % (e[2],))
+            arg = TRUNC_UNIT[e[2].lower()]
+        elif op in DATE_FN_ARG_OPS:
+            n = e[2]
+            if isinstance(n, bool) or not isinstance(n, int) or not -(1 << 31) <= n < (1 << 31):
+                raise PredicateError("%s: the day count must be an int in the int32 range, got %r" % (op, n))
+            arg = n if op == "date_add" else ((-n + (1 << 31)) % (1 << 32)) - (1 << 31)  # Int subtraction wraps
+        emit(x)
+        p.ops.append((DATE_FN_CODE[op], arg))
+
+    def fn_fits(a, b):
+        """A date function's result `a` against `b`: a literal of its kind or NULL, or a column or
+        function result of the same family (dr_filter's own rule)."""
+        if a[0] not in DATE_FN_CODE:
+            return
+        rt, ot = value_type(a), value_type(b)
+        same = (ot == "date") if rt == "date" else (ot in _INT_TYPES)
+        if b[0] == "lit":
+            if b[2] is not None and not same:
+                raise PredicateError("a %s literal does not fit the result of %s (%s)" % (b[1], a[0], rt))
+        elif not same and not (b[0] == "col" and ot is None):  # an unknown column is reported by col()
+            raise PredicateError("the result of %s (%s) does not compare with %s%s"
+                                 % (a[0], rt, b[0], " of type %s" % ot if ot else ""))
+
+    def boolean(op, e):
+        """A date function's result is an integer or a date, no boolean (dr_filter's own rule)."""
+        if e[0] in DATE_FN_CODE:
+            raise PredicateError("%s: the operand must be a boolean, found the result of %s (%s)"
+                                 % (op, e[0], value_type(e)) if op else
+                                 "a predicate must be a boolean, found the result of %s (%s)" % (e[0], value_type(e)))
+
     def emit(e):
         op = e[0]
         if op == "col":
@@ -519,23 +595,36 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
             emit(e[1])
             for l in e[2]:
                 fits(e[1], l)
+                fn_fits(e[1], l)
+                fn_fits(l, e[1])
                 emit(l)
             p.ops.append((OP_CODE["in"], len(e[2])))
         elif op in ("isnull", "isnotnull", "not"):
+            if op == "not":
+                boolean(op, e[1])
             emit(e[1])
             p.ops.append((OP_CODE[op], 0))
         elif op in PATTERN_OPS:
             pattern(e)
+        elif op in DATE_FN_CODE:
+            date_fn(e)
         elif op in OP_CODE:
-            if op not in ("and", "or"):
+            if op in ("and", "or"):
+                boolean(op, e[1])
+                boolean(op, e[2])
+            else:
                 fits(e[1], e[2])
                 fits(e[2], e[1])
+                fn_fits(e[1], e[2])
+                fn_fits(e[2], e[1])
             emit(e[1])
             emit(e[2])
             p.ops.append((OP_CODE[op], 0))
         else:
             raise PredicateError("unsupported expression %r" % (op,))
 
+    for e in preds:
+        boolean(None, e)
     emit(preds[0])
     for e in preds[1:]:
         emit(e)

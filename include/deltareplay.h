@@ -458,7 +458,31 @@ int dr_parsed_release(dr_parsed* parsed);
  * 1..0xFFFF, a surrogate escape, or a pattern that is not valid UTF-8.
  * A partition value that is not valid UTF-8 (Java decodes it with replacement characters first:
  * parity unpinned) is read as characters of one non-continuation byte plus the continuation bytes
- * after it, continuation bytes before the first other byte being one character each. */
+ * after it, continuation bytes before the first other byte being one character each.
+ *
+ * Date functions (DR_OP_YEAR .. DR_OP_TRUNC_DATE, added within ABI 4; an older library answers
+ * "unknown predicate opcode"): each pops one value and pushes one, so they nest
+ * (`COL ts, TO_DATE, DATE_ADD 1, YEAR`). The operand must be a DR_OP_COL or another of these
+ * functions whose result type is the function's operand type -- DR_T_TIMESTAMP for DR_OP_TO_DATE,
+ * DR_T_DATE for the others; a literal operand (Catalyst has folded those), a NULL one included, a
+ * column of another type, a non-zero arg where none is taken or a DR_OP_TRUNC_DATE unit outside 0..3
+ * is DR_E_INVALID_ARG naming the op index and what was found, before any device work. A function
+ * result of type DR_T_INT compares (= != < <= > >= <=>, IN) with BYTE, SHORT, INT or LONG literals,
+ * one of type DR_T_DATE with DATE literals, both with NULL; against a column or another function
+ * result both sides must be integer kinds (BYTE .. LONG) or both DATE; anything else is
+ * DR_E_INVALID_ARG naming the literal or the op. IS [NOT] NULL of a function result is legal; a
+ * function result under AND / OR / NOT or as the program's value (an INT or a DATE, no boolean) is
+ * DR_E_INVALID_ARG.
+ * Spark 3.1 semantics (Year, Quarter, Month, DayOfMonth, DayOfWeek, DayOfYear, WeekOfYear,
+ * Cast(timestamp AS date), DateAdd / DateSub, TruncDate of datetimeExpressions.scala over
+ * DateTimeUtils): the calendar is the proleptic Gregorian one of java.time.LocalDate.ofEpochDay
+ * (no Julian switch: 1582-10-10 is a day); a NULL operand gives NULL, and every function is total,
+ * so no result is NULL for a non-NULL operand. DayOfWeek is Sunday = 1 .. Saturday = 7; WeekOfYear
+ * the ISO-8601 week (Monday first, week 1 holds the year's first Thursday); Cast(ts AS date) is
+ * floorDiv(micros, 86 400 000 000), the session zone being UTC; DateAdd a 32-bit wrapping add
+ * (non-ANSI `Int +`); TruncDate the first day of the year / quarter / month, or the Monday on or
+ * before. A format TruncDate does not know makes its result NULL: the caller lowers that to a NULL
+ * literal. A truncation below day -2^31 (Math.toIntExact throws in Spark) is unpinned. */
 enum dr_pred_type { DR_T_STRING = 0, DR_T_BYTE = 1, DR_T_SHORT = 2, DR_T_INT = 3, DR_T_LONG = 4,
                     DR_T_DATE = 5, DR_T_BOOLEAN = 6,
                     /* Cast(string AS float / double / timestamp (session zone UTC) / binary /
@@ -475,7 +499,13 @@ enum dr_pred_opcode {
   DR_OP_ISNULL = 10, DR_OP_ISNOTNULL = 11,
   DR_OP_AND = 12, DR_OP_OR = 13, DR_OP_NOT = 14,
   DR_OP_STARTSWITH = 15, DR_OP_ENDSWITH = 16, DR_OP_CONTAINS = 17,  /* arg unused (0) */
-  DR_OP_LIKE = 18     /* arg = the escape character as a code point (Spark's default '\\' = 92) */
+  DR_OP_LIKE = 18,    /* arg = the escape character as a code point (Spark's default '\\' = 92) */
+  /* date functions: one operand, one result; arg 0 unless said otherwise */
+  DR_OP_YEAR = 19, DR_OP_QUARTER = 20, DR_OP_MONTH = 21, DR_OP_DAYOFMONTH = 22,  /* DATE -> INT */
+  DR_OP_DAYOFWEEK = 23, DR_OP_DAYOFYEAR = 24, DR_OP_WEEKOFYEAR = 25,             /* DATE -> INT */
+  DR_OP_TO_DATE = 26,     /* TIMESTAMP -> DATE: Cast(ts AS date), session zone UTC */
+  DR_OP_DATE_ADD = 27,    /* DATE -> DATE; arg = the signed day count (DateSub(x, n): -n) */
+  DR_OP_TRUNC_DATE = 28   /* DATE -> DATE; arg = 0 YEAR, 1 QUARTER, 2 MONTH, 3 WEEK */
 };
 typedef struct dr_pred_op { int32_t opcode; int32_t arg; } dr_pred_op;
 
