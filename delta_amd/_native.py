@@ -44,11 +44,16 @@ SYMBOLS = [
     "dr_replay_sharded", "dr_staged_release", "dr_staged_bytes", "dr_staged_plan",
     "dr_replay_staged",
     "dr_replay", "dr_state_release", "dr_state_apply", "dr_state_counts", "dr_state_local_counts", "dr_state_nonfile_json", "dr_state_check_checksum",
-    "dr_state_export", "dr_state_export_plan", "dr_state_export_range", "dr_state_export_rows", "dr_state_lookup_paths", "dr_range_release", "dr_state_materialize", "dr_state_record_sums", "dr_state_record_hashes", "dr_state_write_checkpoint", "dr_state_set_nonfile_json", "dr_filter", "dr_state_scan_order", "dr_state_partition_groups", "dr_free", "dr_last_timings", "dr_set_timing", "dr_set_timing_only",
+    "dr_state_export", "dr_state_export_plan", "dr_state_export_range", "dr_state_export_rows", "dr_state_lookup_paths", "dr_range_release", "dr_state_materialize", "dr_state_record_sums", "dr_state_record_hashes", "dr_state_write_checkpoint", "dr_state_set_nonfile_json", "dr_filter", "dr_state_stats_column", "dr_state_scan_order", "dr_state_partition_groups", "dr_free", "dr_last_timings", "dr_set_timing", "dr_set_timing_only",
     "dr_shard_plan", "dr_stage_log_shard", "dr_shard_begin", "dr_shard_pack", "dr_shard_reduce",
     "dr_shard_finish", "dr_shard_release", "dr_parse_commits", "dr_parsed_release",
 ]
 DR_SHARD_REC_BYTES = 32
+# where a predicate column comes from: bits 24..27 of its type (include/deltareplay.h DR_SRC_*)
+DR_SRC_SHIFT, DR_SRC_MASK = 24, 0xf << 24
+DR_SRC_PARTITION, DR_SRC_STATS_MIN, DR_SRC_STATS_MAX, DR_SRC_STATS_NULLCOUNT, DR_SRC_STATS_NUMRECORDS = 0, 1, 2, 3, 4
+# additions within ABI 4 that a library from before lacks: looked up, and done without when absent
+OPTIONAL_SYMBOLS = ("dr_state_stats_column",)
 
 
 class dr_file(C.Structure):
@@ -170,6 +175,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dr_state_lookup_paths": ([vp, vp, vp, i64, C.c_uint32, vp, vp], C.c_int),
         "dr_range_release": ([vp], C.c_int),
         "dr_filter": ([vp, C.POINTER(dr_predicate), C.POINTER(_P64), _P64], C.c_int),
+        "dr_state_stats_column": ([vp, C.c_char_p, i32, C.POINTER(_P64), C.POINTER(C.POINTER(C.c_uint8)), _P64], C.c_int),
         "dr_state_write_checkpoint": ([vp, i32, i32, C.c_uint32, C.c_uint64, C.POINTER(C.POINTER(C.c_uint8)),
                                        C.POINTER(C.c_uint64), _P64, _P64], C.c_int),
         "dr_state_scan_order": ([vp, C.POINTER(_P64), _P64], C.c_int),
@@ -190,10 +196,19 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dr_parsed_release": ([vp], C.c_int),
     }
     for name, (args, res) in sig.items():
+        if name in OPTIONAL_SYMBOLS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
     return lib
+
+
+def has_stats_sources(lib: C.CDLL) -> bool:
+    """The library reads statistics sources (DR_SRC_STATS_*) on predicate columns: told by the presence
+    of dr_state_stats_column. An older one would take such a column for a partition column of that
+    name, so nothing sends one without asking here first."""
+    return hasattr(lib, "dr_state_stats_column")
 
 
 _LIB = None

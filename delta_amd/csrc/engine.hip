@@ -3516,6 +3516,41 @@ static void fix_fp_values(dr_ctx* ctx, dr_state::PvCol& col, const DBuf<uint64_t
   HIP_OK(hipStreamSynchronize(stream));
 }
 
+// One K5 cache column of n files, its buffers by its type; `pc`: the kernels' view of it (its type
+// without the source: the evaluators compare it with the bare dr_pred_type codes).
+static std::unique_ptr<dr_state::PvCol> new_pv_col(dr_ctx* ctx, uint64_t n, const std::string& name, int32_t type, PvColumn& pc) {
+  auto col = std::make_unique<dr_state::PvCol>();
+  col->name = name;
+  col->type = type;
+  col->isnull = DBuf<uint8_t>(ctx, n);
+  pc.type = type & ~int32_t(DR_SRC_MASK);
+  pc.isnull = col->isnull.p;
+  const int base = type & 0xff;
+  if (base == DR_T_STRING || base == DR_T_BINARY) {
+    col->sptr = DBuf<uint64_t>(ctx, n);
+    col->slen = DBuf<uint32_t>(ctx, n);
+    col->s8 = DBuf<uint64_t>(ctx, n);
+    pc.sptr = col->sptr.p;
+    pc.slen = col->slen.p;
+    pc.s8 = col->s8.p;
+  } else if (base == DR_T_LONG || base == DR_T_DOUBLE || base == DR_T_TIMESTAMP || base == DR_T_DECIMAL) {
+    col->w64 = DBuf<int64_t>(ctx, n);
+    pc.w64 = col->w64.p;
+    if (base == DR_T_DECIMAL) {
+      col->w64hi = DBuf<int64_t>(ctx, n);
+      pc.w64hi = col->w64hi.p;
+      if (((type >> 8) & 0xff) <= 9) {
+        col->w32 = DBuf<uint32_t>(ctx, n);
+        pc.w32 = col->w32.p;
+      }
+    }
+  } else {
+    col->w32 = DBuf<uint32_t>(ctx, n);
+    pc.w32 = col->w32.p;
+  }
+  return col;
+}
+
 // Builds the K5 cache columns `want` (name, type) of st's live AddFiles in one k_pv_extract pass.
 static void build_pv_columns(dr_state& st, const std::vector<std::pair<std::string, int32_t>>& want) {
   dr_ctx* ctx = st.ctx;
@@ -3597,39 +3632,7 @@ static void build_pv_columns(dr_state& st, const std::vector<std::pair<std::stri
   a.col_name_off = d_name_off.p;
   a.col_names = d_names.p;
   std::vector<std::unique_ptr<dr_state::PvCol>> made;
-  for (size_t c = 0; c < want.size(); ++c) {
-    auto col = std::make_unique<dr_state::PvCol>();
-    col->name = want[c].first;
-    col->type = want[c].second;
-    col->isnull = DBuf<uint8_t>(ctx, n);
-    PvColumn& pc = a.cols[c];
-    pc.type = col->type;
-    pc.isnull = col->isnull.p;
-    const int base = col->type & 0xff;
-    if (base == DR_T_STRING || base == DR_T_BINARY) {
-      col->sptr = DBuf<uint64_t>(ctx, n);
-      col->slen = DBuf<uint32_t>(ctx, n);
-      col->s8 = DBuf<uint64_t>(ctx, n);
-      pc.sptr = col->sptr.p;
-      pc.slen = col->slen.p;
-      pc.s8 = col->s8.p;
-    } else if (base == DR_T_LONG || base == DR_T_DOUBLE || base == DR_T_TIMESTAMP || base == DR_T_DECIMAL) {
-      col->w64 = DBuf<int64_t>(ctx, n);
-      pc.w64 = col->w64.p;
-      if (base == DR_T_DECIMAL) {
-        col->w64hi = DBuf<int64_t>(ctx, n);
-        pc.w64hi = col->w64hi.p;
-        if (((col->type >> 8) & 0xff) <= 9) {
-          col->w32 = DBuf<uint32_t>(ctx, n);
-          pc.w32 = col->w32.p;
-        }
-      }
-    } else {
-      col->w32 = DBuf<uint32_t>(ctx, n);
-      pc.w32 = col->w32.p;
-    }
-    made.push_back(std::move(col));
-  }
+  for (size_t c = 0; c < want.size(); ++c) made.push_back(new_pv_col(ctx, n, want[c].first, want[c].second, a.cols[c]));
   // counters: 0 arena fill, 1 arena need, 2.. per column: float / double values left to the host
   const size_t nc = want.size();
   DBuf<unsigned long long> ctr(ctx, 2 + nc);
@@ -3670,9 +3673,75 @@ static void build_pv_columns(dr_state& st, const std::vector<std::pair<std::stri
   for (auto& c : made) st.pv_cols.push_back(std::move(c));
 }
 
+// Builds the statistics cache columns `want` (path, type with its DR_SRC_STATS_* source) of st's live
+// AddFiles in one k_stats_extract pass over the live side's resident export columns (materialised on
+// first use: one source for JSON lines, checkpoint rows and applied states, the line's escaping gone).
+static void build_stats_columns(dr_state& st, const std::vector<std::pair<std::string, int32_t>>& want) {
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  const DevExport& X = materialize(st, DR_LIVE);
+  const uint64_t n = X.n;
+  if (n != st.n_live) fail(DR_E_INTERNAL, "statistics columns: the materialised live side disagrees with the state");
+  StatsExtractArgs a{};
+  a.n = n;
+  a.stats_null = X.stats_null.p;
+  a.stats_off = X.off[EXC_STATS].p;
+  a.stats_bytes = X.stats_bytes.p;
+  const size_t nc = want.size();
+  std::vector<uint64_t> name_off(nc + 1, 0);
+  std::string names;
+  for (size_t c = 0; c < nc; ++c) {
+    names += want[c].first;
+    name_off[c + 1] = names.size();
+  }
+  DBuf<uint64_t> d_name_off = upload(ctx, name_off.data(), name_off.size());
+  DBuf<uint8_t> d_names = upload(ctx, reinterpret_cast<const uint8_t*>(names.data()), names.size());
+  a.ncols = int32_t(nc);
+  a.col_name_off = d_name_off.p;
+  a.col_names = d_names.p;
+  std::vector<std::unique_ptr<dr_state::PvCol>> made;
+  for (size_t c = 0; c < nc; ++c) {
+    a.src[c] = (want[c].second >> DR_SRC_SHIFT) & 0xf;
+    made.push_back(new_pv_col(ctx, n, want[c].first, want[c].second, a.cols[c]));
+  }
+  // counters: 0 arena fill, 1 arena need, 2.. per column: float / double values left to the host
+  DBuf<unsigned long long> ctr(ctx, 2 + nc);
+  DBuf<uint32_t> ferr(ctx, 1);
+  ctr.zero(stream);
+  ferr.zero(stream);
+  a.arena_fill = ctr.p;
+  a.arena_need = ctr.p + 1;
+  a.error = ferr.p;
+  for (size_t c = 0; c < nc; ++c) a.cols[c].nhard = ctr.p + 2 + c;
+  launch_stats_extract(a, stream);
+  const std::vector<unsigned long long> cnt = d2h(ctr.p, 2 + nc, stream);
+  std::vector<DBuf<uint64_t>> hard(nc);
+  bool rerun = cnt[1] != 0;
+  for (size_t c = 0; c < nc; ++c)
+    if (cnt[2 + c]) {
+      hard[c] = DBuf<uint64_t>(ctx, 3 * cnt[2 + c]);
+      a.cols[c].hard = hard[c].p;
+      rerun = true;
+    }
+  if (rerun) {  // escaped string values (into an arena) or numbers for the host's strtod: with those buffers
+    if (cnt[1]) {
+      auto arena = std::make_shared<DBuf<uint8_t>>(ctx, cnt[1] + 64);
+      a.arena = arena->p;
+      a.arena_cap = cnt[1] + 64;
+      st.pv_arenas.push_back(arena);
+    }
+    HIP_OK(hipMemsetAsync(ctr.p, 0, 8 * (2 + nc), stream));
+    launch_stats_extract(a, stream);
+  }
+  if (d2h_one(ferr.p, stream) & 2u) fail(DR_E_INTERNAL, "statistics value arena overflow");
+  for (size_t c = 0; c < nc; ++c)
+    if (cnt[2 + c]) fix_fp_values(ctx, *made[c], hard[c], cnt[2 + c]);
+  for (auto& c : made) st.pv_cols.push_back(std::move(c));
+}
+
 static PvColumn pv_column(const dr_state::PvCol& c) {
   PvColumn p{};
-  p.type = c.type;
+  p.type = c.type & ~int32_t(DR_SRC_MASK);
   p.w32 = c.w32.p;
   p.w64 = c.w64.p;
   p.sptr = c.sptr.p;
@@ -3761,14 +3830,24 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& given
     std::pair<std::string, int32_t> k{pred.col_names[c], pred.col_types[c]};
     if (!find(k.first, k.second) && std::find(want.begin(), want.end(), k) == want.end()) want.push_back(k);
   }
+  // by source: partition values from the records' own bytes, statistics from the resident stats column
+  std::vector<std::pair<std::string, int32_t>> want_stats;
+  for (auto it = want.begin(); it != want.end();)
+    if (it->second & DR_SRC_MASK) {
+      want_stats.push_back(*it);
+      it = want.erase(it);
+    } else {
+      ++it;
+    }
   if (!want.empty() && st.n_live) build_pv_columns(st, want);
+  if (!want_stats.empty() && st.n_live) build_stats_columns(st, want_stats);
   FilterTypedArgs fa{};
   fa.n_live = st.n_live;
   fa.ncols = pred.ncols;
   for (int32_t c = 0; c < pred.ncols; ++c) {
     dr_state::PvCol* col = find(pred.col_names[c], pred.col_types[c]);
     if (!col) {  // no live files: nothing was built
-      fa.cols[c].type = pred.col_types[c];
+      fa.cols[c].type = pred.col_types[c] & ~int32_t(DR_SRC_MASK);
       continue;
     }
     fa.cols[c] = pv_column(*col);
@@ -6499,6 +6578,70 @@ int dr_filter(dr_state* state, const dr_predicate* pred, int64_t** selected, int
     if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(int64_t));
     *selected = out;
     *nselected = int64_t(v.size());
+  });
+}
+
+// dr_state_stats_column: the cached (or now built) typed column, widened to int64 on the host.
+static void stats_column(dr_state& st, const char* name, int32_t type, std::vector<int64_t>& values, std::vector<uint8_t>& nulls) {
+  DR_STAGE("stats_column", st.ctx->stream);
+  const int32_t src = (type >> DR_SRC_SHIFT) & 0xf, base = type & 0xff;
+  const bool type_known = type >= 0 && ((type & ~int32_t(DR_SRC_MASK)) <= DR_T_BINARY || base == DR_T_DECIMAL);
+  if (!type_known) fail(DR_E_UNSUPPORTED, "unsupported partition column type");
+  if (src == DR_SRC_PARTITION) fail(DR_E_INVALID_ARG, "predicate column 0: dr_state_stats_column takes a statistics source (DR_SRC_STATS_*)");
+  check_column_source(name, type, 0);
+  if (base == DR_T_STRING || base == DR_T_DECIMAL)
+    fail(DR_E_UNSUPPORTED, "dr_state_stats_column: STRING and DECIMAL statistics are read through dr_filter");
+  dr_ctx* ctx = st.ctx;
+  ctx->begin_call();
+  ensure_ready(st);
+  hipStream_t stream = ctx->stream;
+  if (st.sources.empty()) fail(DR_E_INVALID_ARG, "state has no staged segment");
+  values.clear();
+  nulls.clear();
+  if (!st.n_live) return;
+  auto find = [&]() -> dr_state::PvCol* {
+    for (auto& c : st.pv_cols)
+      if (c->name == name && c->type == type) return c.get();
+    return nullptr;
+  };
+  if (!find()) build_stats_columns(st, {{std::string(name), type}});
+  const dr_state::PvCol& col = *find();
+  nulls = d2h(col.isnull.p, st.n_live, stream);
+  if (col.w64.p) {
+    values = d2h(col.w64.p, st.n_live, stream);
+  } else {
+    const std::vector<uint32_t> w = d2h(col.w32.p, st.n_live, stream);
+    values.resize(w.size());
+    for (size_t i = 0; i < w.size(); ++i) values[i] = base == DR_T_FLOAT ? int64_t(w[i]) : int64_t(int32_t(w[i]));
+  }
+  for (size_t i = 0; i < values.size(); ++i)
+    if (nulls[i]) values[i] = 0;
+  ctx->collect_timings();
+}
+
+int dr_state_stats_column(dr_state* state, const char* name, int32_t type_with_source, int64_t** values, uint8_t** isnull,
+                          int64_t* n) {
+  if (!state || !name || !values || !isnull || !n) return DR_E_INVALID_ARG;
+  *values = nullptr;
+  *isnull = nullptr;
+  *n = 0;
+  return guard(state->ctx, [&] {
+    HIP_OK(hipSetDevice(state->ctx->device));
+    std::vector<int64_t> v;
+    std::vector<uint8_t> z;
+    stats_column(*state, name, type_with_source, v, z);
+    int64_t* out = static_cast<int64_t*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(int64_t)));
+    uint8_t* outz = static_cast<uint8_t*>(malloc(std::max<size_t>(z.size(), 1)));
+    if (!out || !outz) {
+      free(out);
+      free(outz);
+      throw std::bad_alloc();
+    }
+    if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(int64_t));
+    if (!z.empty()) memcpy(outz, z.data(), z.size());
+    *values = out;
+    *isnull = outz;
+    *n = int64_t(v.size());
   });
 }
 

@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "date_fn.h"
 #include "like_lane.h"
+#include "stats_json.h"
 #include "../../include/deltareplay.h"
 #include <hipcub/device/device_merge_sort.hpp>
 #include <cstddef>
@@ -699,6 +700,106 @@ __global__ void __launch_bounds__(256) k_pv_extract(PvExtractArgs a) {
   }
 }
 
+// ---- k_stats_extract -----------------------------------------------------------------------------
+// Per-file statistics as typed cache columns: one lane per live file walks the file's `stats` string
+// once (stats_json.h) for every wanted column of the call, then converts each token by Spark's
+// JacksonParser rules (include/deltareplay.h, DR_SRC_*): anything else is NULL. The byte walk is
+// per lane and uncoalesced; it is paid once per state and column set.
+// A DATE or TIMESTAMP string that holds escapes is unescaped into a lane-local buffer first; one of
+// more than 256 raw bytes reads as NULL (only leading blanks make a well-formed one that long).
+__device__ __noinline__ bool stats_datetime(const sj::Found& f, bool ts, int64_t* out) {
+  if (f.kind == sj::SJ_STRING_RAW) return ts ? parse_timestamp(f.ptr, f.len, out) : parse_date(f.ptr, f.len, out);
+  if (f.kind != sj::SJ_STRING_ESCAPED || f.len > 256) return false;
+  uint8_t buf[256];
+  const uint32_t m = json_unescape(f.ptr, f.len, buf);  // never longer than its input
+  return ts ? parse_timestamp(buf, m, out) : parse_date(buf, m, out);
+}
+__device__ __forceinline__ bool stats_word(const sj::Found& f, const char* w, uint32_t wl) {
+  if (f.kind != sj::SJ_STRING_RAW || f.len != wl) return false;
+  for (uint32_t k = 0; k < wl; ++k)
+    if (f.ptr[k] != uint8_t(w[k])) return false;
+  return true;
+}
+
+__global__ void __launch_bounds__(256) k_stats_extract(StatsExtractArgs a) {
+  const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  sj::Want want[PV_MAXC];
+  sj::Found found[PV_MAXC];
+  for (int c = 0; c < a.ncols; ++c) {
+    want[c] = sj::Want{a.src[c], a.col_names + a.col_name_off[c], uint32_t(a.col_name_off[c + 1] - a.col_name_off[c])};
+    found[c] = sj::Found{nullptr, 0, sj::SJ_ABSENT};
+  }
+  if (!a.stats_null[i]) sj::locate(a.stats_bytes + a.stats_off[i], a.stats_off[i + 1] - a.stats_off[i], want, a.ncols, found);
+  for (int c = 0; c < a.ncols; ++c) {
+    const PvColumn& col = a.cols[c];
+    const sj::Found f = found[c];
+    const int base = col.type & 0xff;
+    if (base == DR_T_FLOAT || base == DR_T_DOUBLE) {
+      uint64_t bits = 0;
+      int r = FP_NULL;
+      if (f.kind == sj::SJ_NUMBER || stats_word(f, "NaN", 3) || stats_word(f, "Infinity", 8) || stats_word(f, "-Infinity", 9))
+        r = parse_fp(f.ptr, f.len, base == DR_T_FLOAT, &bits);
+      col.isnull[i] = r != FP_OK;
+      if (base == DR_T_FLOAT) col.w32[i] = uint32_t(bits);
+      else col.w64[i] = int64_t(bits);
+      if (r == FP_HARD) {  // the host converts it, as for a partition value (fix_fp_values)
+        const unsigned long long k = atomicAdd(col.nhard, 1ull);
+        if (col.hard) {  // null on the counting pass
+          col.hard[3 * k] = i;
+          col.hard[3 * k + 1] = reinterpret_cast<uint64_t>(f.ptr);
+          col.hard[3 * k + 2] = f.len;
+        }
+      }
+    } else if (base == DR_T_DECIMAL) {
+      uint64_t lo = 0;
+      int64_t hi = 0;
+      const bool ok = f.kind == sj::SJ_NUMBER && parse_decimal(f.ptr, f.len, (col.type >> 8) & 0xff, (col.type >> 16) & 0xff, &lo, &hi);
+      col.isnull[i] = !ok;
+      col.w64[i] = int64_t(lo);
+      col.w64hi[i] = hi;
+      if (col.w32) col.w32[i] = uint32_t(lo);
+    } else if (base == DR_T_TIMESTAMP || base == DR_T_DATE) {
+      int64_t v = 0;
+      const bool ok = stats_datetime(f, base == DR_T_TIMESTAMP, &v);
+      col.isnull[i] = !ok;
+      if (base == DR_T_TIMESTAMP) col.w64[i] = ok ? v : 0;
+      else col.w32[i] = ok ? uint32_t(int32_t(v)) : 0u;
+    } else if (base == DR_T_STRING) {
+      const uint8_t* p = f.ptr;
+      uint32_t len = f.len;
+      bool ok = f.kind == sj::SJ_STRING_RAW;
+      if (f.kind == sj::SJ_STRING_ESCAPED) {  // unescaped into the arena (sized by a counting pass)
+        if (!a.arena) {
+          atomicAdd(a.arena_need, (unsigned long long)len);
+        } else {
+          const unsigned long long o = atomicAdd(a.arena_fill, (unsigned long long)len);
+          if (o + len > a.arena_cap) {
+            atomicOr(a.error, 2u);
+          } else {
+            uint8_t* dst = a.arena + o;
+            len = json_unescape(p, len, dst);
+            p = dst;
+            ok = true;
+          }
+        }
+      }
+      col.isnull[i] = !ok;
+      col.sptr[i] = ok ? reinterpret_cast<uint64_t>(p) : 0ull;
+      col.slen[i] = ok ? len : 0u;
+      uint64_t s8 = 0;
+      for (uint32_t k = 0; k < 8; ++k) s8 = (s8 << 8) | (ok && k < len ? p[k] : 0u);
+      col.s8[i] = s8;
+    } else {  // BYTE .. LONG: -?[0-9]+ inside the type's range (a JSON number has no '+' and no blank)
+      int64_t v = 0;
+      const bool ok = f.kind == sj::SJ_NUMBER && parse_int(f.ptr, f.len, base, &v);
+      col.isnull[i] = !ok;
+      if (base == DR_T_LONG) col.w64[i] = ok ? v : 0;
+      else col.w32[i] = ok ? uint32_t(int32_t(v)) : 0u;
+    }
+  }
+}
+
 // ---- k_filter_typed ------------------------------------------------------------------------------
 // One non-string cache value as the evaluators compare it (kind = leaf_kind(col.type), uniform):
 // LONG / TIMESTAMP and a DECIMAL's low word as stored, DOUBLE / FLOAT as their order keys, the
@@ -1161,9 +1262,10 @@ __device__ __forceinline__ bool dict_key(const PvColumn& c, uint64_t i, uint64_t
 // Inserts (key, row) into an open-addressing table (tag 0 empty, ~0 being written, 1 + row taken),
 // one probe step per loop iteration for every lane, so a lane that finds a slot being written by
 // another lane of its wave retries after that lane's write instead of spinning past it. Returns
-// false when the table is full.
+// false when no slot was found within `limit` probe steps (limit = mask: the table is full).
 template <bool Lds>
-__device__ __forceinline__ bool dict_put(uint64_t* keys, uint32_t* tags, uint32_t mask, uint64_t key, uint32_t row) {
+__device__ __forceinline__ bool dict_put(uint64_t* keys, uint32_t* tags, uint32_t mask, uint64_t key, uint32_t row,
+                                         uint32_t limit) {
   uint32_t h = uint32_t(dict_mix(key) >> 15) & mask;
   uint32_t probes = 0;
   bool done = false, ok = true;
@@ -1181,7 +1283,7 @@ __device__ __forceinline__ bool dict_put(uint64_t* keys, uint32_t* tags, uint32_
         done = true;
       } else {
         h = (h + 1) & mask;
-        if (++probes > mask) { done = true; ok = false; }
+        if (++probes > limit) { done = true; ok = false; }
       }
     }
   }
@@ -1189,6 +1291,16 @@ __device__ __forceinline__ bool dict_put(uint64_t* keys, uint32_t* tags, uint32_
 }
 
 constexpr uint32_t DICT_T = 256, DICT_PER = 8, DICT_LSLOTS = 1024;
+// A usable dictionary holds fewer than DICT_MAX keys in DICT_SLOTS slots (load below 1/2), where a probe
+// run of DICT_PROBES steps does not occur; a column of many more distinct values (a min or max statistic)
+// fills the table, and every later insert would walk all of it. So a global insert gives up after
+// DICT_PROBES steps, and once one has given up (ctr[1]) the others are not tried: the dictionary is
+// abandoned either way, and the leaf kernels read the typed column.
+constexpr uint32_t DICT_PROBES = 4096;
+__device__ __forceinline__ void dict_put_global(const PvDictArgs& a, uint64_t key, uint32_t row) {
+  if (__hip_atomic_load(&a.ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  if (!dict_put<false>(a.key_tab, a.tag_tab, DICT_SLOTS - 1, key, row, DICT_PROBES)) atomicOr(&a.ctr[1], 1ull);
+}
 __global__ void __launch_bounds__(DICT_T) k_dict_insert(PvDictArgs a) {
   __shared__ uint64_t lkey[DICT_LSLOTS];
   __shared__ uint32_t ltag[DICT_LSLOTS];
@@ -1200,13 +1312,12 @@ __global__ void __launch_bounds__(DICT_T) k_dict_insert(PvDictArgs a) {
     const uint64_t i = base + threadIdx.x + uint64_t(j) * DICT_T;
     uint64_t key;
     if (i < a.n && dict_key(a.col, i, &key))
-      if (!dict_put<true>(lkey, ltag, DICT_LSLOTS - 1, key, uint32_t(i)))
-        if (!dict_put<false>(a.key_tab, a.tag_tab, DICT_SLOTS - 1, key, uint32_t(i))) atomicOr(&a.ctr[1], 1ull);
+      if (!dict_put<true>(lkey, ltag, DICT_LSLOTS - 1, key, uint32_t(i), DICT_LSLOTS - 1)) dict_put_global(a, key, uint32_t(i));
   }
   __syncthreads();
   for (uint32_t k = threadIdx.x; k < DICT_LSLOTS; k += DICT_T) {
     const uint32_t t = ltag[k];
-    if (t && !dict_put<false>(a.key_tab, a.tag_tab, DICT_SLOTS - 1, lkey[k], t - 1u)) atomicOr(&a.ctr[1], 1ull);
+    if (t) dict_put_global(a, lkey[k], t - 1u);
   }
 }
 
@@ -1472,6 +1583,9 @@ static inline unsigned g256(uint64_t n) { return unsigned((n + 255) / 256); }
 
 void launch_pv_extract(const PvExtractArgs& a, hipStream_t st) {
   if (a.n_live) DR_LAUNCH(dev::k_pv_extract, dim3(g256(a.n_live)), dim3(256), 0, st, a);
+}
+void launch_stats_extract(const StatsExtractArgs& a, hipStream_t st) {
+  if (a.n) DR_LAUNCH(dev::k_stats_extract, dim3(g256(a.n)), dim3(256), 0, st, a);
 }
 uint64_t filter_leaf_groups(uint64_t n) { return (n + dev::FL_FILES - 1) / dev::FL_FILES; }
 uint32_t filter_leaf_mask_words() { return dev::FL_FILES / 64; }

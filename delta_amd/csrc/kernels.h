@@ -497,6 +497,29 @@ struct PvExtractArgs {
   unsigned long long* arena_need;
   uint32_t* error;
 };
+// k_stats_extract: per-file statistics as typed cache columns (data skipping). One lane per live file
+// locates every wanted (source, path) of the call in the file's `stats` string (stats_json.h) -- the
+// live side's resident export columns, whatever the record came from -- and converts the tokens by
+// Spark's JacksonParser rules into ordinary PvColumns, so the dictionary build and the three
+// evaluators read them as they read partition columns.
+struct StatsExtractArgs {
+  uint64_t n;                    // live files, export order
+  const uint8_t* stats_null;     // [n] 1: the record has no stats
+  const uint64_t* stats_off;     // [n + 1] into stats_bytes
+  const uint8_t* stats_bytes;
+  int32_t ncols;
+  int32_t src[PV_MAXC];          // DR_SRC_STATS_MIN .. DR_SRC_STATS_NUMRECORDS
+  const uint64_t* col_name_off;  // [ncols + 1] the paths (segments joined by 0x01)
+  const uint8_t* col_names;
+  PvColumn cols[PV_MAXC];        // type: the dr_pred_type without its source
+  // unescaped string values (null arena: count the bytes needed into arena_need)
+  uint8_t* arena;
+  uint64_t arena_cap;
+  unsigned long long* arena_fill;
+  unsigned long long* arena_need;
+  uint32_t* error;               // bit 1: arena overflow
+};
+void launch_stats_extract(const StatsExtractArgs& a, hipStream_t st);
 struct FilterTypedArgs {
   uint64_t n_live;
   int32_t ncols;

@@ -8,6 +8,7 @@
 
 #include "date_fn.h"
 #include "like_lane.h"
+#include "stats_json.h"
 
 namespace dr {
 
@@ -16,6 +17,40 @@ namespace dr {
 // scale included), a FLOAT column also a DOUBLE literal (the value is widened), and a literal of one
 // of those types fits no other column. STRING, the integer kinds, DATE and BOOLEAN among themselves
 // are not checked.
+// A column's type as the rules below and the evaluators read it: without its source (DR_SRC_*), which
+// says where the engine finds the values and nothing about how they compare.
+static int32_t col_type(const dr_predicate& p, int32_t c) { return p.col_types[c] & ~int32_t(DR_SRC_MASK); }
+static int32_t col_source(const dr_predicate& p, int32_t c) { return (p.col_types[c] >> DR_SRC_SHIFT) & 0xf; }
+
+void check_column_source(const char* name, int32_t type_with_source, int32_t c) {
+  const int32_t src = (type_with_source >> DR_SRC_SHIFT) & 0xf, base = type_with_source & 0xff;
+  if (src == DR_SRC_PARTITION) return;
+  if (src > DR_SRC_STATS_NUMRECORDS)
+    fail(DR_E_INVALID_ARG, fmt("predicate column %d: unknown source %d (DR_SRC_PARTITION .. DR_SRC_STATS_NUMRECORDS)", c, src));
+  if ((src == DR_SRC_STATS_MIN || src == DR_SRC_STATS_MAX) && (base == DR_T_BOOLEAN || base == DR_T_BINARY))
+    fail(DR_E_INVALID_ARG, fmt("predicate column %d: %s statistics have no %s (type %d)", c, src == DR_SRC_STATS_MIN ? "minValues" : "maxValues",
+                               base == DR_T_BOOLEAN ? "BOOLEAN" : "BINARY", base));
+  if ((src == DR_SRC_STATS_NULLCOUNT || src == DR_SRC_STATS_NUMRECORDS) && (type_with_source & ~int32_t(DR_SRC_MASK)) != DR_T_LONG)
+    fail(DR_E_INVALID_ARG, fmt("predicate column %d: %s is a LONG, not type %d", c, src == DR_SRC_STATS_NULLCOUNT ? "nullCount" : "numRecords",
+                               type_with_source & ~int32_t(DR_SRC_MASK)));
+  const size_t len = std::strlen(name);
+  if (src == DR_SRC_STATS_NUMRECORDS) {
+    if (len) fail(DR_E_INVALID_ARG, fmt("predicate column %d: numRecords takes the name \"\", not a path of %zu bytes", c, len));
+    return;
+  }
+  if (len > size_t(sj::SJ_MAXPATH))
+    fail(DR_E_INVALID_ARG, fmt("predicate column %d: a statistics path has at most %d bytes, not %zu", c, sj::SJ_MAXPATH, len));
+  int segs = 1;
+  for (size_t q = 0; q <= len; ++q) {
+    const bool end = q == len || uint8_t(name[q]) == sj::SJ_SEP;
+    if (end && (q == 0 || uint8_t(name[q - 1]) == sj::SJ_SEP))
+      fail(DR_E_INVALID_ARG, fmt("predicate column %d: segment %d of the statistics path is empty", c, segs - 1));
+    if (end && q < len) ++segs;
+  }
+  if (segs > sj::SJ_MAXSEG)
+    fail(DR_E_INVALID_ARG, fmt("predicate column %d: a statistics path has at most %d segments, not %d", c, sj::SJ_MAXSEG, segs));
+}
+
 static bool new_pred_type(int32_t t) { return (t & 0xff) >= DR_T_FLOAT; }
 static bool lit_fits(int32_t ctype, int32_t ltype) {
   if (!new_pred_type(ctype) && !new_pred_type(ltype)) return true;
@@ -46,7 +81,8 @@ static const char* pattern_op_name(int op) {
 }
 static std::string pred_op_text(const dr_predicate& p, int32_t k) {
   const int op = p.ops[k].opcode, arg = p.ops[k].arg;
-  if (op == DR_OP_COL) return fmt("partition column %s of type %d", p.col_names[arg], p.col_types[arg]);
+  if (op == DR_OP_COL)
+    return fmt("%s column %s of type %d", col_source(p, arg) ? "statistics" : "partition", p.col_names[arg], col_type(p, arg));
   if (op == DR_OP_LIT) return p.lit_null[arg] ? std::string("a NULL literal") : fmt("literal %d of type %d", arg, p.lit_types[arg]);
   return fmt("the result of op %d (opcode %d)", k, op);
 }
@@ -60,7 +96,7 @@ static lk::LikeCompiled compile_like(const dr_predicate& p, int32_t lit, int32_t
 static void check_pattern_op(const dr_predicate& p, int32_t k, int32_t vk, int32_t pk) {
   const int op = p.ops[k].opcode;
   const char* name = pattern_op_name(op);
-  if (p.ops[vk].opcode != DR_OP_COL || p.col_types[p.ops[vk].arg] != DR_T_STRING)
+  if (p.ops[vk].opcode != DR_OP_COL || col_type(p, p.ops[vk].arg) != DR_T_STRING)
     fail(DR_E_INVALID_ARG, fmt("predicate op %d (%s): the value must be a STRING partition column, found %s", k, name,
                                pred_op_text(p, vk).c_str()));
   const int32_t l = p.ops[pk].arg;
@@ -134,7 +170,7 @@ static bool int_kind(int32_t t) { return t >= DR_T_BYTE && t <= DR_T_LONG; }
 // result; -1 for anything else (a boolean).
 static int32_t value_type(const dr_predicate& p, int32_t k) {
   const int op = p.ops[k].opcode, arg = p.ops[k].arg;
-  return op == DR_OP_COL ? p.col_types[arg] : op == DR_OP_LIT ? p.lit_types[arg] : is_date_fn(op) ? date_fn_result(op) : -1;
+  return op == DR_OP_COL ? col_type(p, arg) : op == DR_OP_LIT ? p.lit_types[arg] : is_date_fn(op) ? date_fn_result(op) : -1;
 }
 // Function op k over the operand rooted at op vk: a column or a function of the operand type, then the arg.
 static void check_date_fn(const dr_predicate& p, int32_t k, int32_t vk) {
@@ -241,9 +277,11 @@ void check_program(const dr_predicate& p) {
     const int32_t prec = (t >> 8) & 0xff, scale = t >> 16;
     return prec >= 1 && prec <= 38 && scale <= prec;
   };
-  for (int32_t c = 0; c < p.ncols; ++c)
-    if (!type_ok(p.col_types[c]) || !p.col_names[c])
+  for (int32_t c = 0; c < p.ncols; ++c) {
+    if (p.col_types[c] < 0 || !type_ok(col_type(p, c)) || !p.col_names[c])
       fail(DR_E_UNSUPPORTED, "unsupported partition column type");
+    check_column_source(p.col_names[c], p.col_types[c], c);
+  }
   for (int32_t k = 0; k < p.nlits; ++k) {
     if (p.lit_null[k]) continue;
     const int32_t t = p.lit_types[k];
@@ -264,9 +302,9 @@ void check_program(const dr_predicate& p) {
   auto fits = [&](int32_t ck, int32_t lk) {
     if (p.ops[ck].opcode != DR_OP_COL || p.ops[lk].opcode != DR_OP_LIT) return;
     const int32_t c = p.ops[ck].arg, l = p.ops[lk].arg;
-    if (!p.lit_null[l] && !lit_fits(p.col_types[c], p.lit_types[l]))
+    if (!p.lit_null[l] && !lit_fits(col_type(p, c), p.lit_types[l]))
       fail(DR_E_INVALID_ARG, fmt("predicate literal %d (type %d) does not fit partition column %s (type %d)", l,
-                                 p.lit_types[l], p.col_names[c], p.col_types[c]));
+                                 p.lit_types[l], p.col_names[c], col_type(p, c)));
   };
   // op by op, so that the first fault in program order is the one reported: its indices, its place in
   // the tree, then its operands
@@ -364,7 +402,7 @@ bool leafify(const dr_predicate& p, LeafPlan& L) {
   auto is_str = [](int32_t t) { return leaf_kind(t) == DR_T_STRING; };
   // string (and binary) columns with literals of bytes, others numeric; the new types by lit_fits
   auto kind_ok = [&](int32_t col, int32_t lit) {
-    return is_str(p.col_types[col]) == is_str(p.lit_types[lit]) && lit_fits(p.col_types[col], p.lit_types[lit]);
+    return is_str(col_type(p, col)) == is_str(p.lit_types[lit]) && lit_fits(col_type(p, col), p.lit_types[lit]);
   };
   // a FLOAT column's literal as the leaf compares it: a DOUBLE literal's key as it is (the leaf widens
   // the value, pad = 2), and then a FLOAT literal's key widened like the value
@@ -429,7 +467,7 @@ bool leafify(const dr_predicate& p, LeafPlan& L) {
         const int32_t c = f.col;
         // a function result: an integer against an integer literal, whatever the column (check_program)
         if (!f.nfn && !p.lit_null[l] && !kind_ok(c, l)) return false;
-        const bool widen = !f.nfn && !p.lit_null[l] && p.col_types[c] == DR_T_FLOAT && p.lit_types[l] == DR_T_DOUBLE;
+        const bool widen = !f.nfn && !p.lit_null[l] && col_type(p, c) == DR_T_FLOAT && p.lit_types[l] == DR_T_DOUBLE;
         f.lit = slot(l);
         f.lit_null = p.lit_null[l] ? 1 : 0;
         f.pad = widen ? 2 : 0;
@@ -452,14 +490,14 @@ bool leafify(const dr_predicate& p, LeafPlan& L) {
         f.op = DR_OP_IN;
         const int32_t c = f.col;
         // a function result is a 32-bit integer: a sorted set or a bitmap, like an INT column's
-        const int kind = f.nfn ? DR_T_INT : leaf_kind(p.col_types[c]);
+        const int kind = f.nfn ? DR_T_INT : leaf_kind(col_type(p, c));
         const bool str = kind == DR_T_STRING;
         bool has_null = false, widen = false;
         std::vector<int64_t> iv;
         std::vector<std::pair<int64_t, uint64_t>> dv;  // decimals: (high signed, low unsigned)
         std::vector<std::string> sv;
         for (size_t q = 1; q < ch.n; ++q)  // a FLOAT column with a DOUBLE element: all in binary64
-          widen |= !f.nfn && is_lit(ch[q]) && !p.lit_null[p.ops[ch[q]].arg] && p.col_types[c] == DR_T_FLOAT &&
+          widen |= !f.nfn && is_lit(ch[q]) && !p.lit_null[p.ops[ch[q]].arg] && col_type(p, c) == DR_T_FLOAT &&
                    p.lit_types[p.ops[ch[q]].arg] == DR_T_DOUBLE;
         for (size_t q = 1; q < ch.n; ++q) {
           if (!is_lit(ch[q])) return false;

@@ -17,6 +17,9 @@ inline bool is_date_fn(int op) { return op >= DR_OP_YEAR && op <= DR_OP_TRUNC_DA
 // Host validation of the postfix program: types, literals, operand indices and stack discipline.
 // The only function here that accepts an unchecked program; the others take one it has passed.
 void check_program(const dr_predicate& p);
+// What check_program asks of column c's source (bits 24..27 of its type, DR_SRC_*): a known one, a type
+// the statistic has, a path within stats_json.h's limits. DR_SRC_PARTITION passes as it is.
+void check_column_source(const char* name, int32_t type_with_source, int32_t c);
 
 // Literal k as the evaluators compare it: FLOAT / DOUBLE as their order keys (fp_key32 / fp_key64,
 // the device's own functions), a DECIMAL's two words, everything else as given.

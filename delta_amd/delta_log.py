@@ -589,6 +589,8 @@ class State:
 
     def filter(self, program) -> List[int]:
         from .predicates import lower_program
+        if any(t & N.DR_SRC_MASK for _, t in program.cols) and not N.has_stats_sources(self.eng.lib):
+            raise DeltaError(N.DR_E_UNSUPPORTED, "this libdeltareplay predates statistics sources on predicate columns")
         pred, keep = lower_program(program)
         sel = C.POINTER(C.c_int64)()
         n = C.c_int64()
@@ -597,6 +599,34 @@ class State:
         res = [sel[i] for i in range(n.value)]
         self.eng.lib.dr_free(C.cast(sel, C.c_void_p))
         return res
+
+    def stats_column(self, source: int, path: Sequence[str] = (), typ: str = "long"):
+        """dr_state_stats_column: one typed statistics column of the live files in export order, as
+        (values np.int64[n], isnull np.uint8[n]). `source` is N.DR_SRC_STATS_MIN .. _NUMRECORDS, `path`
+        the data column's field names (one for a top-level column; none for numRecords), `typ` its Spark
+        type name. Integer kinds, date days and timestamp micros come back as they are, float and double
+        as their bits. `stats_column(N.DR_SRC_STATS_NUMRECORDS)` is what a count(*) from metadata sums."""
+        import numpy as np
+        from .predicates import type_code, PredicateError
+        code = type_code(typ)
+        if code is None:
+            raise PredicateError("unsupported statistics type %r" % (typ,))
+        if not N.has_stats_sources(self.eng.lib):
+            raise DeltaError(N.DR_E_UNSUPPORTED, "this libdeltareplay has no dr_state_stats_column")
+        name = "\x01".join([path] if isinstance(path, str) else list(path)).encode("utf-8")
+        vals = C.POINTER(C.c_int64)()
+        nulls = C.POINTER(C.c_uint8)()
+        n = C.c_int64()
+        with self.eng.lock:
+            self.eng.check(self.eng.lib.dr_state_stats_column(self.h, name, code | int(source) << N.DR_SRC_SHIFT,
+                                                              C.byref(vals), C.byref(nulls), C.byref(n)))
+        try:
+            v = np.ctypeslib.as_array(vals, shape=(max(n.value, 1),))[:n.value].copy()
+            z = np.ctypeslib.as_array(nulls, shape=(max(n.value, 1),))[:n.value].copy()
+        finally:
+            self.eng.lib.dr_free(C.cast(vals, C.c_void_p))
+            self.eng.lib.dr_free(C.cast(nulls, C.c_void_p))
+        return v, z
 
     def write_checkpoint_part(self, part: int, parts: int, stats: bool = True, parsed: bool = True,
                               row_group_rows: int = 0, snappy: bool = True, with_adds: bool = False):
@@ -794,20 +824,28 @@ class Snapshot:
         from .predicates import partition_schema
         return partition_schema(self.metadata)
 
-    def _scan_rows(self, filters: Sequence) -> Optional[List[int]]:
-        """Live positions kept by the metadata-only conjuncts of `filters` (None: no pruning)."""
+    def _scan_rows(self, filters: Sequence, data_skipping: bool = False) -> Optional[List[int]]:
+        """Live positions kept by the metadata-only conjuncts of `filters` (None: no pruning) and, with
+        `data_skipping`, by the data conjuncts rewritten over the per-file statistics (skipping.py),
+        ANDed onto them in the same dr_filter call."""
         from .predicates import split_metadata_and_data_predicates, build_program
         parts = (self.metadata or {}).get("partitionColumns") or []
         meta_preds = []
         for f in filters:
             meta_preds.extend(split_metadata_and_data_predicates(f, parts)[0])
+        if data_skipping:
+            from .skipping import skipping_predicates, fit_limits
+            # only as many as one dr_filter program holds (16 columns, its stack): dropping one is sound
+            meta_preds.extend(fit_limits(self.partition_schema(), meta_preds, skipping_predicates(filters, self.metadata)))
         if not meta_preds:
             return None
         return self.state.filter(build_program(self.partition_schema(), meta_preds))
 
-    def files_for_scan(self, filters: Sequence) -> List[dict]:
-        """PartitionFiltering.filesForScan: metadata-only conjuncts, evaluated on the GPU."""
-        sel = self._scan_rows(filters)
+    def files_for_scan(self, filters: Sequence, data_skipping: bool = False) -> List[dict]:
+        """PartitionFiltering.filesForScan: metadata-only conjuncts, evaluated on the GPU. With
+        `data_skipping` the files whose statistics (add.stats) prove that no row passes the data
+        conjuncts are dropped as well; a file without the statistic is kept."""
+        sel = self._scan_rows(filters, data_skipping)
         if sel is not None and self._all is None:
             return self.state.export_rows_records(N.DR_LIVE, sel)  # the pruned rows alone
         files = self.all_files
@@ -889,7 +927,7 @@ class Snapshot:
                              "version %d of:\n%s" % (self.version, mismatch))
         return mismatch
 
-    def list_files(self, partition_filters: Sequence = ()) -> List[Tuple[tuple, List[dict]]]:
+    def list_files(self, partition_filters: Sequence = (), data_skipping: bool = False) -> List[Tuple[tuple, List[dict]]]:
         """TahoeFileIndex.listFiles (D/files/TahoeFileIndex.scala:58-81): the pruned files grouped
         by partitionValues; each group is (partition row cast to the partition schema's types,
         [FileStatus {length, modificationTime, path}]) with paths made absolute under the table
@@ -898,7 +936,7 @@ class Snapshot:
         from urllib.parse import unquote
         from .predicates import cast_partition_value
         schema = self.partition_schema()
-        rows = self._scan_rows(partition_filters)
+        rows = self._scan_rows(partition_filters, data_skipping)  # data filters count only with data_skipping
         groups = self.state.partition_groups(rows)  # grouped on the GPU
         if rows is not None and self._all is None:  # the pruned rows alone, fetched in group order
             order = [i for grp in groups for i in grp]

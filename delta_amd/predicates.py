@@ -89,7 +89,7 @@ def _refs(expr) -> List[str]:
     op = expr[0]
     if op == "col":
         return [expr[1]]
-    if op == "lit":
+    if op == "lit" or op == "stats":  # a statistics column (skipping.py) names no table column
         return []
     if op == "in":
         return _refs(expr[1]) + [r for l in expr[2] for r in _refs(l)]
@@ -466,7 +466,7 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
     if not preds:
         raise PredicateError("no predicates")
     p = Program()
-    colidx: Dict[str, int] = {}
+    colidx: Dict[object, int] = {}  # partition columns by name, statistics by (source, path)
     parts = list(schema)
 
     def col(name):
@@ -480,6 +480,17 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
             colidx[exact] = len(p.cols)
             p.cols.append((exact, type_code(typ)))
         p.ops.append((OP_COL, colidx[exact]))
+
+    def stats_col(e):
+        """("stats", source, path, type): a per-file statistic as a column whose type carries the
+        source (DR_SRC_STATS_*); its name is the path's segments joined by 0x01."""
+        if len(e) != 4 or type_code(e[3]) is None:
+            raise PredicateError("bad statistics column %r" % (e,))
+        key = (int(e[1]), "\x01".join(e[2]))
+        if key not in colidx:
+            colidx[key] = len(p.cols)
+            p.cols.append((key[1], type_code(e[3]) | key[0] << N.DR_SRC_SHIFT))
+        p.ops.append((OP_COL, colidx[key]))
 
     def lit(typ, v):
         value = _lit(typ, v)
@@ -504,7 +515,9 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
             raise PredicateError("%s takes a column and a literal%s" % (op, " and an optional escape" if op == "like" else ""))
         value, pat = e[1], e[2]
         exact = _resolve(value[1], parts) if value[0] == "col" else None
-        if value[0] != "col":
+        if value[0] == "stats" and len(value) == 4 and value[3] == "string":
+            pass  # a string statistic: the op's operand rule looks at the type alone
+        elif value[0] != "col":
             raise PredicateError("%s: the value must be a string partition column, found %r" % (op, value[0]))
         if exact is not None and schema[exact] != "string":
             raise PredicateError("%s: the value must be a string partition column, %s is %s" % (op, exact, schema[exact]))
@@ -530,6 +543,8 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
             return schema[exact] if exact is not None else None
         if e[0] == "lit":
             return e[1]
+        if e[0] == "stats":
+            return e[3] if len(e) == 4 else None
         if e[0] in DATE_FN_CODE:
             return "integer" if DATE_FN_CODE[e[0]] < DATE_FN_CODE["to_date"] else "date"
         return None
@@ -542,14 +557,14 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
                                                   "an expression and a day count" if op in DATE_FN_ARG_OPS else "one expression"))
         want = "timestamp" if op == "to_date" else "date"
         x = e[1]
-        if not isinstance(x, tuple) or (x[0] != "col" and x[0] not in DATE_FN_CODE):
+        if not isinstance(x, tuple) or (x[0] not in ("col", "stats") and x[0] not in DATE_FN_CODE):
             raise PredicateError("%s: the operand must be a %s partition column or date function, found %r"
                                  % (op, want, x[0] if isinstance(x, tuple) else x))
         if x[0] == "col" and _resolve(x[1], parts) is None:
             col(x[1])  # raises: no partition column
         if value_type(x) != want:
             raise PredicateError("%s: the operand must be a %s value, found %s of type %s"
-                                 % (op, want, "column %s" % x[1] if x[0] == "col" else x[0], value_type(x)))
+                                 % (op, want, "column %s" % (x[1],) if x[0] in ("col", "stats") else x[0], value_type(x)))
         arg = 0
         if op == "trunc":
             if not isinstance(e[2], str) or e[2].lower() not in TRUNC_UNIT:
@@ -591,6 +606,8 @@ def build_program(schema: Dict[str, str], preds: Sequence) -> Program:
             col(e[1])
         elif op == "lit":
             lit(e[1], e[2])
+        elif op == "stats":
+            stats_col(e)
         elif op == "in":
             emit(e[1])
             for l in e[2]:

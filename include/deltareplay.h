@@ -41,7 +41,11 @@ extern "C" {
  *      also within ABI 4, no signature or struct changed: dr_filter takes partition columns and literals
  *      of DR_T_FLOAT .. DR_T_DECIMAL (encodings at dr_pred_type). A library from before answers
  *      DR_E_UNSUPPORTED ("unsupported partition column type") for such a column, as it always did; the
- *      host then keeps that conjunct on its own side */
+ *      host then keeps that conjunct on its own side
+ *      also within ABI 4: a source in bits 24..27 of a predicate column's type (DR_SRC_*, per-file
+ *      statistics as predicate columns) and dr_state_stats_column. A library from before would read a
+ *      statistics column as a partition column of that name, so a host looks dr_state_stats_column up
+ *      and sends no such column when the symbol is absent */
 #define DR_ABI_VERSION 4
 
 /* Status codes. The JNI shim rethrows the reference's exception class with dr_last_error():
@@ -509,6 +513,33 @@ enum dr_pred_opcode {
 };
 typedef struct dr_pred_op { int32_t opcode; int32_t arg; } dr_pred_op;
 
+/* Where a predicate column comes from (added within ABI 4): bits 24..27 of its col_types entry; bits
+ * 0..7 stay the dr_pred_type and bits 8..23 a decimal's p and s. DR_SRC_PARTITION (0) is
+ * partitionValues[name], so every earlier program means what it meant. The others read the file's
+ * `stats` JSON (PROTOCOL.md, "Per-file Statistics") -- data skipping: the host rewrites a data filter
+ * into a predicate over these columns that is TRUE or NULL-guarded for every file that may hold a
+ * matching row (delta_amd/skipping.py has the rules), and ANDs it onto the partition program.
+ * col_names[k] of a statistics column is the data column's path: its field names, exactly as the JSON
+ * keys, joined by the byte 0x01 for a leaf of a nested struct; at most 8 segments and 255 bytes, no
+ * empty segment; "" for DR_SRC_STATS_NUMRECORDS.
+ * DR_SRC_STATS_MIN / _MAX take BYTE, SHORT, INT, LONG, DATE, TIMESTAMP, FLOAT, DOUBLE, DECIMAL(p, s)
+ * and STRING; _NULLCOUNT and _NUMRECORDS are DR_T_LONG. Anything else -- a source above 4 included --
+ * is DR_E_INVALID_ARG naming the column index, before any device work. String patterns and date
+ * functions keep their own operand rules, which look at the dr_pred_type alone.
+ * Values, by the JSON token (Spark's JacksonParser; anything else is NULL, as is every column of a
+ * file whose stats are null, absent, `{}` or no well-formed JSON object): the integer kinds, NULLCOUNT
+ * and NUMRECORDS from a number of the form -?[0-9]+ inside the type's range (1e3, 1.0 and a string
+ * are NULL); FLOAT / DOUBLE from any number, correctly rounded, and from the strings "NaN",
+ * "Infinity", "-Infinity"; DECIMAL from a number, rounded HALF_UP to s, NULL beyond p digits; DATE and
+ * TIMESTAMP from a string in Cast(string AS date / timestamp)'s grammar (Delta writes
+ * yyyy-MM-dd'T'HH:mm:ss.SSSXXX; the lenient forms only the cast accepts are parity-unpinned); STRING
+ * from a string, escapes resolved. A repeated key keeps its last value. The first use of a
+ * statistics column materialises the live side (dr_state_materialize) and caches the typed column. */
+#define DR_SRC_SHIFT 24
+#define DR_SRC_MASK (0xf << DR_SRC_SHIFT)
+enum dr_pred_source { DR_SRC_PARTITION = 0, DR_SRC_STATS_MIN = 1, DR_SRC_STATS_MAX = 2,
+                      DR_SRC_STATS_NULLCOUNT = 3, DR_SRC_STATS_NUMRECORDS = 4 };
+
 typedef struct dr_predicate {
   int32_t nops; const dr_pred_op* ops;
   int32_t ncols; const char* const* col_names; const int32_t* col_types;
@@ -517,6 +548,15 @@ typedef struct dr_predicate {
 } dr_predicate;
 
 int dr_filter(dr_state* state, const dr_predicate* pred, int64_t** selected, int64_t* nselected);
+/* One typed statistics column of the live side in DR_LIVE export order (an addition within ABI 4):
+ * `name` and `type_with_source` as a predicate column's (source DR_SRC_STATS_MIN ..
+ * DR_SRC_STATS_NUMRECORDS). *values has *n entries -- the integer kinds, DATE days and TIMESTAMP
+ * micros as int64, FLOAT (zero-extended) and DOUBLE as their bits, 0 where (*isnull)[i] != 0 -- what a
+ * count(*) answered from metadata, summing numRecords, reads. Both arrays are freed with dr_free.
+ * DR_E_UNSUPPORTED for STRING and DECIMAL (reachable through dr_filter); DR_E_INVALID_ARG, naming
+ * column 0, for what a predicate column of that source is refused for, and for DR_SRC_PARTITION. */
+int dr_state_stats_column(dr_state* state, const char* name, int32_t type_with_source, int64_t** values,
+                          uint8_t** isnull, int64_t* n);
 void dr_free(void* p);
 
 /* ---- checkpoint writer --------------------------------------------------

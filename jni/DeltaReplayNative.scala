@@ -71,6 +71,11 @@ object DeltaReplayNative {
   @native def rangeRelease(range: Long): Unit
   @native def filter(state: Long, program: Array[Byte]): Array[Long]
   @native def scanOrder(state: Long): Array[Long]
+  /** One typed statistics column of the live files (dr_state_stats_column): `name` is the data column's path,
+   *  its field names joined by the byte 0x01 (empty for numRecords), `typ` the dr_pred_type code with the
+   *  DR_SRC_STATS_* source in bits 24..27. Returns Array(values: Array[Long], nulls: Array[Byte]). The glue
+   *  links the symbol: a library it loads with also reads statistics sources in `filter` programs. */
+  @native def stateStatsColumn(state: Long, name: Array[Byte], typ: Int): Array[AnyRef]
   @native def partitionGroups(state: Long, rows: Array[Long]): Array[Array[Long]]
   /** dr_lines' columns; handleOut(0) receives the parse to release with parsedRelease. */
   @native def parseCommits(ctx: Long, staged: Long, handleOut: Array[Long]): Array[ByteBuffer]

@@ -723,6 +723,51 @@ NATIVE(jlongArray, filter)(JNIEnv* env, jobject self, jlong state, jbyteArray pr
   return out;
 }
 
+/* One typed statistics column of the live files (dr_state_stats_column): `name` the data column's path
+ * (segments joined by 0x01, UTF-8; empty for numRecords), `type` the dr_pred_type with its DR_SRC_STATS_*
+ * source in bits 24..27. Returns {values, nulls}: values(i) the statistic of live file i as a long (FLOAT /
+ * DOUBLE: the bits), nulls(i) != 0 where the file has none. This glue links the symbol, so a library that
+ * loads under it reads statistics sources in `filter` programs too. */
+NATIVE(jobjectArray, stateStatsColumn)(JNIEnv* env, jobject self, jlong state, jbyteArray name, jint type) {
+  (void)self;
+  if (!name) {
+    throw_status(env, DR_E_INVALID_ARG, "stateStatsColumn: name is null");
+    return NULL;
+  }
+  const jsize len = (*env)->GetArrayLength(env, name);
+  char* path = (char*)malloc((size_t)len + 1);
+  if (!path) {
+    throw_status(env, DR_E_OOM, "stateStatsColumn: out of memory");
+    return NULL;
+  }
+  (*env)->GetByteArrayRegion(env, name, 0, len, (jbyte*)path);
+  path[len] = 0;
+  int64_t* values = NULL;
+  uint8_t* nulls = NULL;
+  int64_t n = 0;
+  if (memchr(path, 0, (size_t)len)) {
+    free(path);
+    throw_status(env, DR_E_INVALID_ARG, "stateStatsColumn: name holds a NUL byte");
+    return NULL;
+  }
+  const int rc = dr_state_stats_column((dr_state*)(intptr_t)state, path, (int32_t)type, &values, &nulls, &n);
+  free(path);
+  CHECK_STATE(env, rc, (intptr_t)state, NULL);
+  jlongArray v = long_array(env, values, n);
+  jbyteArray z = (*env)->NewByteArray(env, (jsize)n);
+  if (z && n) (*env)->SetByteArrayRegion(env, z, 0, (jsize)n, (const jbyte*)nulls);
+  dr_free(values);
+  dr_free(nulls);
+  if (!v || !z) return NULL;
+  jclass object_class = (*env)->FindClass(env, "java/lang/Object");
+  if (!object_class) return NULL;  /* its exception is pending */
+  jobjectArray out = (*env)->NewObjectArray(env, 2, object_class, NULL);
+  if (!out) return NULL;
+  (*env)->SetObjectArrayElement(env, out, 0, v);
+  (*env)->SetObjectArrayElement(env, out, 1, z);
+  return out;
+}
+
 /* DeltaSourceSnapshot.initialFiles' order (D/files/DeltaSourceSnapshot.scala:53-95). */
 NATIVE(jlongArray, scanOrder)(JNIEnv* env, jobject self, jlong state) {
   (void)self;
