@@ -44,7 +44,7 @@ SYMBOLS = [
     "dr_replay_sharded", "dr_staged_release", "dr_staged_bytes", "dr_staged_plan",
     "dr_replay_staged",
     "dr_replay", "dr_state_release", "dr_state_apply", "dr_state_counts", "dr_state_local_counts", "dr_state_nonfile_json", "dr_state_check_checksum",
-    "dr_state_export", "dr_state_export_plan", "dr_state_export_range", "dr_state_export_rows", "dr_state_lookup_paths", "dr_range_release", "dr_state_materialize", "dr_state_record_sums", "dr_state_record_hashes", "dr_state_write_checkpoint", "dr_state_set_nonfile_json", "dr_filter", "dr_state_stats_column", "dr_state_scan_order", "dr_state_partition_groups", "dr_free", "dr_last_timings", "dr_set_timing", "dr_set_timing_only",
+    "dr_state_export", "dr_state_export_plan", "dr_state_export_range", "dr_state_export_rows", "dr_state_lookup_paths", "dr_range_release", "dr_state_materialize", "dr_state_record_sums", "dr_state_record_hashes", "dr_state_write_checkpoint", "dr_state_set_nonfile_json", "dr_filter", "dr_state_stats_column", "dr_state_aggregate", "dr_agg_release", "dr_state_scan_order", "dr_state_partition_groups", "dr_free", "dr_last_timings", "dr_set_timing", "dr_set_timing_only",
     "dr_shard_plan", "dr_stage_log_shard", "dr_shard_begin", "dr_shard_pack", "dr_shard_reduce",
     "dr_shard_finish", "dr_shard_release", "dr_parse_commits", "dr_parsed_release",
 ]
@@ -52,8 +52,13 @@ DR_SHARD_REC_BYTES = 32
 # where a predicate column comes from: bits 24..27 of its type (include/deltareplay.h DR_SRC_*)
 DR_SRC_SHIFT, DR_SRC_MASK = 24, 0xf << 24
 DR_SRC_PARTITION, DR_SRC_STATS_MIN, DR_SRC_STATS_MAX, DR_SRC_STATS_NULLCOUNT, DR_SRC_STATS_NUMRECORDS = 0, 1, 2, 3, 4
+# dr_state_aggregate (include/deltareplay.h enum dr_agg_fn, dr_agg_input)
+DR_AGG_COUNT, DR_AGG_MIN, DR_AGG_MAX, DR_AGG_SUM = 0, 1, 2, 3
+DR_AGG_IN_COLUMN, DR_AGG_IN_SIZE, DR_AGG_IN_MTIME = 0, 1, 2
+DR_AGG_MAX_SPECS = 16
+AGG_TILE = 1024  # selection positions per workgroup of k_agg_tiles (delta_amd/csrc/kernels.h AGG_TILE)
 # additions within ABI 4 that a library from before lacks: looked up, and done without when absent
-OPTIONAL_SYMBOLS = ("dr_state_stats_column",)
+OPTIONAL_SYMBOLS = ("dr_state_stats_column", "dr_state_aggregate", "dr_agg_release")
 
 
 class dr_file(C.Structure):
@@ -107,6 +112,16 @@ class dr_predicate(C.Structure):
                 ("nlits", C.c_int32), ("lit_types", C.POINTER(C.c_int32)),
                 ("lit_i64", _P64), ("lit_null", _PU8),
                 ("lit_str_off", _P64), ("lit_str_bytes", _PU8)]
+
+
+class dr_agg_spec(C.Structure):
+    _fields_ = [("fn", C.c_int32), ("input", C.c_int32), ("name", C.c_char_p), ("type_with_source", C.c_int32)]
+
+
+class dr_agg_result(C.Structure):
+    _fields_ = [("ngroups", C.c_int64), ("naggs", C.c_int32),
+                ("group_rows", _P64), ("nonnull", _P64), ("value_lo", _P64), ("value_hi", _P64),
+                ("arg_row", _P64), ("str_off", _P64), ("str_bytes", _PU8)]
 
 
 def hip_runtimes() -> list:
@@ -176,6 +191,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dr_range_release": ([vp], C.c_int),
         "dr_filter": ([vp, C.POINTER(dr_predicate), C.POINTER(_P64), _P64], C.c_int),
         "dr_state_stats_column": ([vp, C.c_char_p, i32, C.POINTER(_P64), C.POINTER(C.POINTER(C.c_uint8)), _P64], C.c_int),
+        "dr_state_aggregate": ([vp, _P64, i64, _P64, i64, C.POINTER(dr_agg_spec), i32, C.POINTER(vp),
+                                C.POINTER(dr_agg_result)], C.c_int),
+        "dr_agg_release": ([vp], C.c_int),
         "dr_state_write_checkpoint": ([vp, i32, i32, C.c_uint32, C.c_uint64, C.POINTER(C.POINTER(C.c_uint8)),
                                        C.POINTER(C.c_uint64), _P64, _P64], C.c_int),
         "dr_state_scan_order": ([vp, C.POINTER(_P64), _P64], C.c_int),
@@ -209,6 +227,11 @@ def has_stats_sources(lib: C.CDLL) -> bool:
     of dr_state_stats_column. An older one would take such a column for a partition column of that
     name, so nothing sends one without asking here first."""
     return hasattr(lib, "dr_state_stats_column")
+
+
+def has_aggregate(lib: C.CDLL) -> bool:
+    """The library reduces on the device (dr_state_aggregate / dr_agg_release, added within ABI 4)."""
+    return hasattr(lib, "dr_state_aggregate") and hasattr(lib, "dr_agg_release")
 
 
 _LIB = None

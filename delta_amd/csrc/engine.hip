@@ -6645,6 +6645,183 @@ int dr_state_stats_column(dr_state* state, const char* name, int32_t type_with_s
   });
 }
 
+// dr_state_aggregate's result: one host block that holds every array of the dr_agg_result. It is plain
+// host memory with no tie to its context or state, so it outlives both; live handles are registered so
+// that a second release is refused instead of freeing twice.
+struct dr_agg {
+  std::vector<int64_t> words;   // group_rows, nonnull, value_lo, value_hi, arg_row, str_off
+  std::vector<uint8_t> bytes;   // str_bytes
+};
+static std::mutex g_aggs_mu;
+static std::unordered_set<dr_agg*> g_aggs;
+
+// The reduction of `aggs` over the selection (k_agg.hip). The arguments have passed check_agg_specs and
+// check_agg_selection. rows and group_off are uploaded whole (8 B a row: 80 MB for 10M selected files,
+// against the columns' own bytes that then stay on the device); size and modificationTime are read from
+// the materialised live side, which the statistics columns are built from as well.
+static void aggregate_state(dr_state& st, const int64_t* rows, uint64_t n, const int64_t* group_off, uint64_t ngroups,
+                            const dr_agg_spec* aggs, int32_t naggs, dr_agg& R, dr_agg_result* out) {
+  DR_STAGE("aggregate", st.ctx->stream);
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  const uint64_t cells = uint64_t(naggs) * ngroups;
+  // the block: group_rows [ngroups], four arrays of [cells], str_off [cells + 1]
+  R.words.assign(ngroups + 4 * cells + cells + 1, 0);
+  int64_t* group_rows = R.words.data();
+  int64_t* nonnull = group_rows + ngroups;
+  int64_t* value_lo = nonnull + cells;
+  int64_t* value_hi = value_lo + cells;
+  int64_t* arg_row = value_hi + cells;
+  int64_t* str_off = arg_row + cells;
+  for (uint64_t g = 0; g < ngroups; ++g) group_rows[g] = group_off ? group_off[g + 1] - group_off[g] : int64_t(n);
+  std::fill(arg_row, arg_row + cells, int64_t(-1));
+  if (n && cells) {
+    auto find = [&](const std::string& name, int32_t type) -> dr_state::PvCol* {
+      for (auto& c : st.pv_cols)
+        if (c->name == name && c->type == type) return c.get();
+      return nullptr;
+    };
+    // the specs' columns in the K5 cache (built for the ones not there yet, by source as dr_filter does)
+    std::vector<std::pair<std::string, int32_t>> want, want_stats;
+    bool builtin = false;
+    for (int32_t a = 0; a < naggs; ++a) {
+      if (aggs[a].input != DR_AGG_IN_COLUMN) {
+        builtin = true;
+        continue;
+      }
+      std::pair<std::string, int32_t> k{aggs[a].name, aggs[a].type_with_source};
+      auto& into = (k.second & DR_SRC_MASK) ? want_stats : want;
+      if (!find(k.first, k.second) && std::find(into.begin(), into.end(), k) == into.end()) into.push_back(k);
+    }
+    if (!want.empty()) build_pv_columns(st, want);
+    if (!want_stats.empty()) build_stats_columns(st, want_stats);
+    const DevExport* X = builtin ? &materialize(st, DR_LIVE) : nullptr;
+    if (X && X->n != st.n_live) fail(DR_E_INTERNAL, "aggregate: the materialised live side disagrees with the state");
+    AggArgs A{};
+    A.n = n;
+    A.ngroups = ngroups;
+    A.naggs = naggs;
+    bool strings = false;
+    for (int32_t a = 0; a < naggs; ++a) {
+      AggSpec& s = A.spec[a];
+      s.fn = aggs[a].fn;
+      if (aggs[a].input != DR_AGG_IN_COLUMN) {
+        s.kind = AGK_I64;
+        s.v = aggs[a].input == DR_AGG_IN_SIZE ? X->size.p : X->mtime.p;
+      } else {
+        const dr_state::PvCol* col = find(aggs[a].name, aggs[a].type_with_source);
+        if (!col) fail(DR_E_INTERNAL, "aggregate: a cache column was not built");
+        const int base = col->type & 0xff;
+        s.isnull = col->isnull.p;
+        if (base == DR_T_STRING || base == DR_T_BINARY) {
+          s.kind = AGK_STR;
+          s.v = col->s8.p;
+          s.sptr = col->sptr.p;
+          s.slen = col->slen.p;
+          strings |= s.fn == DR_AGG_MIN || s.fn == DR_AGG_MAX;
+        } else if (base == DR_T_DECIMAL) {
+          s.kind = AGK_DEC;
+          s.v = col->w64.p;
+          s.hi = col->w64hi.p;
+        } else if (base == DR_T_LONG || base == DR_T_TIMESTAMP || base == DR_T_DOUBLE) {
+          s.kind = base == DR_T_DOUBLE ? AGK_F64 : AGK_I64;
+          s.v = col->w64.p;
+        } else {
+          s.kind = base == DR_T_FLOAT ? AGK_F32 : AGK_I32;
+          s.v = col->w32.p;
+        }
+        if (!s.v) fail(DR_E_INTERNAL, "aggregate: a cache column lacks its values");
+      }
+      if (s.fn == DR_AGG_COUNT) s.kind = AGK_ZERO;
+    }
+    DBuf<int64_t> d_rows, d_off;
+    if (rows) d_rows = upload(ctx, rows, n);
+    const int64_t one_group[2] = {0, int64_t(n)};
+    d_off = upload(ctx, group_off ? group_off : one_group, ngroups + 1);
+    const uint64_t tiles = (n + AGG_TILE - 1) / AGG_TILE;
+    DBuf<AggAcc> part(ctx, tiles * 2 * uint64_t(naggs));
+    DBuf<int64_t> res(ctx, 4 * cells);
+    HIP_OK(hipMemsetAsync(res.p, 0, 3 * cells * 8, stream));
+    HIP_OK(hipMemsetAsync(res.p + 3 * cells, 0xff, cells * 8, stream));
+    A.rows = d_rows.p;
+    A.group_off = d_off.p;
+    A.part = part.p;
+    A.nonnull = res.p;
+    A.value_lo = res.p + cells;
+    A.value_hi = res.p + 2 * cells;
+    A.arg_row = res.p + 3 * cells;
+    launch_agg_tiles(A, stream);
+    launch_agg_combine(A, stream);
+    HIP_OK(hipMemcpyAsync(nonnull, res.p, 4 * cells * 8, hipMemcpyDeviceToHost, stream));
+    if (strings) {
+      // the winners' bytes: lengths per cell, their exclusive scan, one gather into the arena
+      DBuf<uint32_t> len(ctx, cells);
+      DBuf<uint64_t> off(ctx, cells + 1);
+      DBuf<uint8_t> scratch(ctx, scan_scratch_for(cells));
+      launch_agg_str_len(A, len.p, stream);
+      launch_scan_u32(len.p, off.p, cells, ss(scratch), stream);
+      const uint64_t nb = d2h_one(off.p + cells, stream);
+      DBuf<uint8_t> arena(ctx, nb + 1);
+      launch_agg_str_copy(A, off.p, arena.p, stream);
+      HIP_OK(hipMemcpyAsync(str_off, off.p, (cells + 1) * 8, hipMemcpyDeviceToHost, stream));
+      HIP_OK(hipStreamSynchronize(stream));
+      R.bytes = d2h(arena.p, nb, stream);
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+  ctx->collect_timings();
+  out->ngroups = int64_t(ngroups);
+  out->naggs = naggs;
+  out->group_rows = group_rows;
+  out->nonnull = nonnull;
+  out->value_lo = value_lo;
+  out->value_hi = value_hi;
+  out->arg_row = arg_row;
+  out->str_off = str_off;
+  if (R.bytes.empty()) R.bytes.resize(1);
+  out->str_bytes = R.bytes.data();
+}
+
+int dr_state_aggregate(dr_state* state, const int64_t* rows, int64_t nrows, const int64_t* group_off, int64_t ngroups,
+                       const dr_agg_spec* aggs, int32_t naggs, dr_agg** handle, dr_agg_result* out) {
+  if (!state || !handle || !out) return DR_E_INVALID_ARG;
+  *handle = nullptr;
+  memset(out, 0, sizeof(*out));
+  dr_ctx* ctx = state->ctx;
+  const int rc = guard(ctx, [&] {
+    // the arguments first: nothing is built, staged or read through them before they hold
+    check_agg_specs(aggs, naggs);
+    if (state->sharded)
+      fail(DR_E_UNSUPPORTED, "dr_state_aggregate: a sharded state holds this rank's source-side survivors only; "
+                             "a rank's rows are not the table's");
+    HIP_OK(hipSetDevice(ctx->device));
+    ctx->begin_call();
+    ensure_ready(*state);  // the side's size, which the selection is checked against
+    if (state->sources.empty()) fail(DR_E_INVALID_ARG, "state has no staged segment");
+    check_agg_selection(rows, nrows, state->n_live, group_off, ngroups);
+    auto R = std::make_unique<dr_agg>();
+    aggregate_state(*state, rows, rows ? uint64_t(nrows) : state->n_live, group_off, group_off ? uint64_t(ngroups) : 1, aggs,
+                    naggs, *R, out);
+    std::lock_guard<std::mutex> g(g_aggs_mu);
+    g_aggs.insert(R.get());
+    *handle = R.release();
+  });
+  if (rc != DR_OK) {
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::recursive_mutex> g(ctx->api_mu);
+    ctx->drop_timings();
+  }
+  return rc;
+}
+
+int dr_agg_release(dr_agg* handle) {
+  if (!handle) return DR_OK;
+  std::lock_guard<std::mutex> g(g_aggs_mu);
+  if (!g_aggs.erase(handle)) return DR_E_INVALID_ARG;  // not a live handle (released twice)
+  delete handle;
+  return DR_OK;
+}
+
 static int64_t* malloc_copy(const std::vector<int64_t>& v) {
   int64_t* out = static_cast<int64_t*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(int64_t)));
   if (!out) throw std::bad_alloc();

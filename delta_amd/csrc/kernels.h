@@ -996,3 +996,57 @@ void launch_snap_compress(const uint8_t* in, uint64_t n, uint8_t* out, uint32_t*
 void launch_snap_gather(const uint8_t* slots, const uint32_t* len, const uint64_t* off, uint32_t nfrag, uint8_t* dst,
                         hipStream_t st);
 }  // namespace dr
+
+// ---- metadata-only aggregates (k_agg.hip, dr_state_aggregate) ---------------------------------------
+namespace dr {
+constexpr uint32_t AGG_BLOCK = 256;   // threads of a workgroup of either kernel
+constexpr uint32_t AGG_TILE = 1024;   // selection positions per workgroup of k_agg_tiles
+constexpr int32_t AGG_MAXSPEC = 16;   // DR_AGG_MAX_SPECS
+// How a spec's input is read and compared (wave-uniform: one switch per spec, not per lane).
+enum AggKind : int32_t { AGK_ZERO = 0,   // COUNT: no value
+                         AGK_I32 = 1,    // w32, sign-extended (BYTE / SHORT / INT / DATE / BOOLEAN)
+                         AGK_F32 = 2,    // w32 bits under fp_key32
+                         AGK_I64 = 3,    // w64 (LONG / TIMESTAMP / size / modificationTime)
+                         AGK_F64 = 4,    // w64 bits under fp_key64
+                         AGK_DEC = 5,    // w64 (low, unsigned) under w64hi
+                         AGK_STR = 6 };  // bytes through sptr / slen, the first 8 in s8
+struct AggSpec {
+  int32_t fn;             // dr_agg_fn
+  int32_t kind;           // AggKind
+  const void* v;          // w32 / w64 / s8 by kind
+  const int64_t* hi;      // AGK_DEC: w64hi
+  const uint64_t* sptr;   // AGK_STR
+  const uint32_t* slen;
+  const uint8_t* isnull;  // null pointer: never NULL (size, modificationTime)
+};
+// A reduction's running value. SUM: the 128-bit sum in lo / hi. MIN / MAX: the candidate's order key
+// (AGK_STR: lo = s8, hi = its row) and its selection position, -1 while no input was non-NULL.
+struct AggAcc {
+  int64_t nn;   // non-NULL inputs
+  int64_t lo, hi;
+  int64_t pos;
+};
+struct AggArgs {
+  const int64_t* rows;        // [n] live export positions; null pointer: position p is row p
+  uint64_t n;                 // selection size
+  const int64_t* group_off;   // [ngroups + 1], never a null pointer (one group: {0, n})
+  uint64_t ngroups;
+  int32_t naggs;
+  AggSpec spec[AGG_MAXSPEC];
+  AggAcc* part;               // [tiles * 2 * naggs]: a tile's first / last segment when its group goes on beyond the tile
+  // results, [a * ngroups + g]; zeroed (arg_row: -1) before the launch, so an empty group needs no writer
+  int64_t* nonnull;
+  int64_t* value_lo;
+  int64_t* value_hi;
+  int64_t* arg_row;
+};
+// Pass 1: one workgroup per AGG_TILE positions gathers every spec's inputs and reduces them by group
+// (segmented where group boundaries fall in the tile); groups within the tile go to the results, the
+// others leave a partial. Pass 2: the tile a spanning group starts in folds its partials.
+void launch_agg_tiles(const AggArgs& a, hipStream_t st);
+void launch_agg_combine(const AggArgs& a, hipStream_t st);
+// STRING / BINARY MIN / MAX: the winners' lengths per cell (0 for every other cell), then -- behind an
+// exclusive scan of them -- their bytes into the result arena.
+void launch_agg_str_len(const AggArgs& a, uint32_t* len, hipStream_t st);
+void launch_agg_str_copy(const AggArgs& a, const uint64_t* off, uint8_t* bytes, hipStream_t st);
+}  // namespace dr

@@ -51,6 +51,55 @@ void check_column_source(const char* name, int32_t type_with_source, int32_t c) 
     fail(DR_E_INVALID_ARG, fmt("predicate column %d: a statistics path has at most %d segments, not %d", c, sj::SJ_MAXSEG, segs));
 }
 
+void check_agg_specs(const dr_agg_spec* aggs, int32_t naggs) {
+  if (naggs < 0 || naggs > DR_AGG_MAX_SPECS)
+    fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: naggs = %d is outside 0..%d", naggs, DR_AGG_MAX_SPECS));
+  if (naggs && !aggs) fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: aggs == NULL with naggs = %d", naggs));
+  for (int32_t a = 0; a < naggs; ++a) {
+    const dr_agg_spec& s = aggs[a];
+    if (s.fn < DR_AGG_COUNT || s.fn > DR_AGG_SUM)
+      fail(DR_E_INVALID_ARG, fmt("aggregate spec %d: unknown fn %d (DR_AGG_COUNT .. DR_AGG_SUM)", a, s.fn));
+    if (s.input < DR_AGG_IN_COLUMN || s.input > DR_AGG_IN_MTIME)
+      fail(DR_E_INVALID_ARG, fmt("aggregate spec %d: unknown input %d (DR_AGG_IN_COLUMN .. DR_AGG_IN_MTIME)", a, s.input));
+    if (s.input != DR_AGG_IN_COLUMN) {
+      if ((s.name && s.name[0]) || s.type_with_source)
+        fail(DR_E_INVALID_ARG, fmt("aggregate spec %d: %s takes the name \"\" and the type 0", a,
+                                   s.input == DR_AGG_IN_SIZE ? "DR_AGG_IN_SIZE" : "DR_AGG_IN_MTIME"));
+      continue;
+    }
+    if (!s.name) fail(DR_E_INVALID_ARG, fmt("aggregate spec %d: a column input needs a name", a));
+    const int32_t t = s.type_with_source & ~int32_t(DR_SRC_MASK), base = t & 0xff;
+    bool type_ok = s.type_with_source >= 0 && (base == DR_T_DECIMAL || t <= DR_T_BINARY);
+    if (type_ok && base == DR_T_DECIMAL) {
+      const int32_t prec = (t >> 8) & 0xff, scale = t >> 16;
+      type_ok = prec >= 1 && prec <= 38 && scale <= prec;
+    }
+    if (!type_ok) fail(DR_E_INVALID_ARG, fmt("aggregate spec %d: no valid column type (code %d)", a, s.type_with_source));
+    check_column_source(s.name, s.type_with_source, a);
+    if (s.fn == DR_AGG_SUM && (t < DR_T_BYTE || t > DR_T_LONG))
+      fail(DR_E_INVALID_ARG, fmt("aggregate spec %d: SUM takes BYTE .. LONG, size and modificationTime, not type %d", a, t));
+  }
+}
+
+void check_agg_selection(const int64_t* rows, int64_t nrows, uint64_t side, const int64_t* group_off, int64_t ngroups) {
+  if (rows && nrows < 0) fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: nrows = %lld is negative", (long long)nrows));
+  if (group_off && ngroups < 0) fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: ngroups = %lld is negative", (long long)ngroups));
+  const uint64_t n = rows ? uint64_t(nrows) : side;
+  for (uint64_t i = 0; rows && i < n; ++i)
+    if (rows[i] < 0 || uint64_t(rows[i]) >= side)
+      fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: rows[%llu] = %lld is outside [0, %llu)", (unsigned long long)i,
+                                 (long long)rows[i], (unsigned long long)side));
+  if (!group_off) return;
+  if (group_off[0] != 0) fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: group_off[0] = %lld, not 0", (long long)group_off[0]));
+  for (int64_t g = 0; g < ngroups; ++g)
+    if (group_off[g + 1] < group_off[g])
+      fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: group_off[%lld] = %lld is below group_off[%lld] = %lld", (long long)(g + 1),
+                                 (long long)group_off[g + 1], (long long)g, (long long)group_off[g]));
+  if (uint64_t(group_off[ngroups]) != n)
+    fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: group_off[%lld] = %lld, not the selection's %llu rows", (long long)ngroups,
+                               (long long)group_off[ngroups], (unsigned long long)n));
+}
+
 static bool new_pred_type(int32_t t) { return (t & 0xff) >= DR_T_FLOAT; }
 static bool lit_fits(int32_t ctype, int32_t ltype) {
   if (!new_pred_type(ctype) && !new_pred_type(ltype)) return true;

@@ -21,6 +21,14 @@ void check_program(const dr_predicate& p);
 // the statistic has, a path within stats_json.h's limits. DR_SRC_PARTITION passes as it is.
 void check_column_source(const char* name, int32_t type_with_source, int32_t c);
 
+// dr_state_aggregate's host checks (every one DR_E_INVALID_ARG, naming the first offending spec or
+// position). check_agg_specs: naggs in 0..DR_AGG_MAX_SPECS, known fn and input, "" and 0 on a built-in
+// input, a valid column type, what check_column_source asks (its texts, the spec index as the column),
+// SUM over BYTE .. LONG, size and modificationTime only. check_agg_selection: rows within a side of
+// `side` files, group_off from 0 to the selection's size and non-decreasing.
+void check_agg_specs(const dr_agg_spec* aggs, int32_t naggs);
+void check_agg_selection(const int64_t* rows, int64_t nrows, uint64_t side, const int64_t* group_off, int64_t ngroups);
+
 // Literal k as the evaluators compare it: FLOAT / DOUBLE as their order keys (fp_key32 / fp_key64,
 // the device's own functions), a DECIMAL's two words, everything else as given.
 void literal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t* hi);

@@ -660,6 +660,84 @@ class State:
             self.eng.check(self.eng.lib.dr_state_scan_order(self.h, C.byref(out), C.byref(n)))
         return self._take(out, n.value)
 
+    _AGG_FN = {"count": N.DR_AGG_COUNT, "min": N.DR_AGG_MIN, "max": N.DR_AGG_MAX, "sum": N.DR_AGG_SUM}
+
+    @staticmethod
+    def agg_spec(agg) -> "N.dr_agg_spec":
+        """One dr_agg_spec from `(fn, "size")`, `(fn, "mtime")` or `(fn, source, path, typ)`: fn one of
+        count / min / max / sum, source N.DR_SRC_PARTITION or N.DR_SRC_STATS_*, path the partition
+        column's name or the data column's field names (none for numRecords), typ the Spark type name.
+        An N.dr_agg_spec passes as it is."""
+        from .predicates import type_code, PredicateError
+        if isinstance(agg, N.dr_agg_spec):
+            return agg
+        fn = State._AGG_FN.get(agg[0])
+        if fn is None:
+            raise PredicateError("unknown aggregate %r" % (agg[0],))
+        if len(agg) == 2 and agg[1] in ("size", "mtime"):
+            return N.dr_agg_spec(fn, N.DR_AGG_IN_SIZE if agg[1] == "size" else N.DR_AGG_IN_MTIME, b"", 0)
+        _, source, path, typ = agg
+        code = type_code(typ)
+        if code is None:
+            raise PredicateError("unsupported aggregate input type %r" % (typ,))
+        name = "\x01".join([path] if isinstance(path, str) else list(path)).encode("utf-8")
+        return N.dr_agg_spec(fn, N.DR_AGG_IN_COLUMN, name, code | int(source) << N.DR_SRC_SHIFT)
+
+    def aggregate(self, aggs: Sequence, rows=None, groups=None) -> Dict[str, "object"]:
+        """dr_state_aggregate: COUNT / MIN / MAX / SUM of `aggs` (agg_spec forms) over the live export
+        positions `rows` (None: every live file), per group of `groups` (a group_off array of
+        ngroups + 1 offsets into `rows`; None: one group), reduced on the GPU. Returns numpy arrays:
+        group_rows [ngroups]; nonnull, value_lo, value_hi, arg_row [naggs, ngroups]; and strings, a
+        list per agg of the STRING / BINARY MIN / MAX value of each group as bytes (None for every
+        other cell and for a group without a non-NULL input). The meaning of each field is in
+        include/deltareplay.h at dr_state_aggregate."""
+        import numpy as np
+        lib = self.eng.lib
+        if not N.has_aggregate(lib):
+            raise DeltaError(N.DR_E_UNSUPPORTED, "this libdeltareplay has no dr_state_aggregate")
+        specs = [self.agg_spec(a) for a in aggs]
+        arr = (N.dr_agg_spec * max(len(specs), 1))(*specs)
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        g = None if groups is None else np.ascontiguousarray(groups, dtype=np.int64)
+        p64 = C.POINTER(C.c_int64)
+        handle = C.c_void_p()
+        out = N.dr_agg_result()
+        with self.eng.lock:
+            self.eng.check(lib.dr_state_aggregate(
+                self.h, None if r is None else r.ctypes.data_as(p64), 0 if r is None else r.size,
+                None if g is None else g.ctypes.data_as(p64), 0 if g is None else g.size - 1,
+                arr if specs else None, len(specs), C.byref(handle), C.byref(out)))
+        try:
+            ng, na = out.ngroups, out.naggs
+            cells = ng * na
+
+            def take(ptr, n, shape):
+                return np.ctypeslib.as_array(ptr, shape=(max(n, 1),))[:n].copy().reshape(shape)
+            res = {"group_rows": take(out.group_rows, ng, (ng,))}
+            for k in ("nonnull", "value_lo", "value_hi", "arg_row"):
+                res[k] = take(getattr(out, k), cells, (na, ng))
+            off = take(out.str_off, cells + 1, (cells + 1,))
+            blob = bytes(np.ctypeslib.as_array(out.str_bytes, shape=(max(int(off[-1]), 1),))[:int(off[-1])])
+            strings = []
+            for a, s in enumerate(specs):
+                is_str = (s.input == N.DR_AGG_IN_COLUMN and s.fn in (N.DR_AGG_MIN, N.DR_AGG_MAX)
+                          and (s.type_with_source & 0xff) in (0, 10))  # DR_T_STRING, DR_T_BINARY
+                strings.append([blob[off[a * ng + k]:off[a * ng + k + 1]] if is_str and res["arg_row"][a, k] >= 0 else None
+                                for k in range(ng)])
+            res["strings"] = strings
+        finally:
+            lib.dr_agg_release(handle)
+        return res
+
+    def partition_group_offsets(self, rows: Optional[Sequence[int]] = None):
+        """dr_state_partition_groups as it comes: (order, group_off) -- the pair State.aggregate takes
+        as `rows` and `groups`."""
+        groups = self.partition_groups(rows)
+        off = [0]
+        for grp in groups:
+            off.append(off[-1] + len(grp))
+        return [i for grp in groups for i in grp], off
+
     def partition_groups(self, rows: Optional[Sequence[int]] = None) -> List[List[int]]:
         """dr_state_partition_groups: `rows` (live export positions; None = all) grouped by the
         table's partition values on the GPU (TahoeFileIndex.listFiles, D/files/TahoeFileIndex.scala:58-81)."""
@@ -850,6 +928,91 @@ class Snapshot:
             return self.state.export_rows_records(N.DR_LIVE, sel)  # the pruned rows alone
         files = self.all_files
         return list(files) if sel is None else [files[i] for i in sel]
+
+    def scan_sizes(self, filters: Sequence, data_skipping: bool = False) -> Dict[str, Dict[str, Optional[int]]]:
+        """The three DataSize(bytesCompressed, rows) of DeltaScan (D/stats/DeltaScan.scala:29-52), which
+        PartitionFiltering.filesForScan leaves null: `total` over every live file, `partition` after the
+        metadata-only conjuncts of `filters`, `scanned` after data skipping as well (the same as
+        `partition` without `data_skipping`). Each is {"bytesCompressed": sum of size, "rows": sum of
+        numRecords -- None when a counted file lacks it --, "files"}. Computed by dr_filter and
+        dr_state_aggregate: no row leaves the device."""
+        specs = [("sum", "size"), ("sum", N.DR_SRC_STATS_NUMRECORDS, (), "long")]
+
+        def size_of(rows) -> Dict[str, Optional[int]]:
+            r = self.state.aggregate(specs, rows)
+            files = int(r["group_rows"][0])
+            return {"bytesCompressed": int(r["value_lo"][0, 0]),
+                    "rows": int(r["value_lo"][1, 0]) if int(r["nonnull"][1, 0]) == files else None, "files": files}
+        total = size_of(None)
+        part_rows = self._scan_rows(filters, False)
+        partition = total if part_rows is None else size_of(part_rows)
+        if not data_skipping:
+            return {"total": total, "partition": partition, "scanned": dict(partition)}
+        rows = self._scan_rows(filters, True)
+        return {"total": total, "partition": partition, "scanned": dict(total) if rows is None else size_of(rows)}
+
+    def aggregate_from_metadata(self, exprs: Sequence, filters: Sequence = (), by_partition: bool = False):
+        """count / min / max answered from the log's metadata alone, where it proves them. `exprs` is
+        drawn from ("count",), ("count", col), ("min", col), ("max", col) over partition columns and data
+        columns that have statistics; names resolve as in filters (case-insensitively, `a.b` nested).
+        Per group the answer, or None when the metadata does not prove it (and when SQL's answer is NULL):
+          - count(*) needs numRecords on every file;
+          - count(col) of a data column needs nullCount.col on every file as well; of a partition column
+            it is count(*) when no file's value is NULL and 0 when every one is;
+          - min / max of a partition column is always exact;
+          - min / max of a data column is exact only for byte, short, integer, long and date, and only
+            when every file either has the statistic or has nullCount == numRecords;
+          - timestamp, string, float, double and decimal statistics are bounds (truncated or NaN-blind)
+            and give None.
+        `filters` select files by their partition conjuncts; a data conjunct makes every count and every
+        data-column answer None, because skipping keeps files and does not select rows. Values come as
+        aggregates.decode gives them (date: days since the epoch, timestamp: microseconds).
+        Returns the list of answers, one per expression; with `by_partition` a list of (partition row
+        cast to the partition schema's types, answers), the groups of dr_state_partition_groups over the
+        selected files. The reductions run on the GPU (dr_state_aggregate)."""
+        import numpy as np
+        from . import aggregates as A
+        from .predicates import split_metadata_and_data_predicates, build_program, cast_partition_value
+        parts = (self.metadata or {}).get("partitionColumns") or []
+        meta, data = [], []
+        for f in filters:
+            m, d = split_metadata_and_data_predicates(f, parts)
+            meta.extend(m)
+            data.extend(d)
+        plan = A.plan(exprs, self.metadata, data_filter=bool(data))
+        schema = self.partition_schema()
+        rows = self.state.filter(build_program(schema, meta)) if meta else None
+        off = None
+        if by_partition:
+            rows, off = self.state.partition_group_offsets(rows)
+        res = self.state.aggregate(plan.specs, rows, off)
+        ngroups = len(res["group_rows"])
+        # a data column's statistic may be missing where the file holds no non-NULL value of it: those
+        # files are found by one dr_filter per column and counted per group
+        allnull = {}
+        for k, path in plan.allnull:
+            if all(int(res["nonnull"][k][g]) == int(res["group_rows"][g]) for g in range(ngroups)):
+                continue
+            stat = ("stats", plan.specs[k][1], tuple(path), plan.specs[k][3])
+            proven = self.state.filter(build_program(schema, [
+                ("isnull", stat), ("=", ("stats", N.DR_SRC_STATS_NULLCOUNT, tuple(path), "long"),
+                                   ("stats", N.DR_SRC_STATS_NUMRECORDS, (), "long"))]))
+            mark = np.zeros(self.num_of_files + 1, dtype=np.int64)
+            mark[np.asarray(proven, dtype=np.int64)] = 1
+            sel = mark[:self.num_of_files] if rows is None else mark[np.asarray(rows, dtype=np.int64)]
+            cs = np.concatenate([[0], np.cumsum(sel)])
+            o = np.asarray(off if off is not None else [0, len(sel)], dtype=np.int64)
+            allnull[k] = cs[o[1:]] - cs[o[:-1]]
+        answers = A.prove(plan, res, allnull)
+        if not by_partition:
+            return answers[0]
+        firsts = [rows[off[g]] for g in range(ngroups)]
+        recs = self.state.export_rows_records(N.DR_LIVE, firsts) if firsts else []
+        out = []
+        for g, rec in enumerate(recs):
+            pv = rec.get("partitionValues") or {}
+            out.append((tuple(cast_partition_value(pv.get(c), t) for c, t in schema.items()), answers[g]))
+        return out
 
     def files_by_path(self, paths: Sequence) -> List[Optional[dict]]:
         """The AddFile of every path that is a live file of this snapshot, None for every other one --

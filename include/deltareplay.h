@@ -45,7 +45,9 @@ extern "C" {
  *      also within ABI 4: a source in bits 24..27 of a predicate column's type (DR_SRC_*, per-file
  *      statistics as predicate columns) and dr_state_stats_column. A library from before would read a
  *      statistics column as a partition column of that name, so a host looks dr_state_stats_column up
- *      and sends no such column when the symbol is absent */
+ *      and sends no such column when the symbol is absent
+ *      also within ABI 4: dr_state_aggregate / dr_agg_release (COUNT / MIN / MAX / SUM over the typed
+ *      columns, size and modificationTime of a selection, per group); looked up like the others */
 #define DR_ABI_VERSION 4
 
 /* Status codes. The JNI shim rethrows the reference's exception class with dr_last_error():
@@ -557,6 +559,72 @@ int dr_filter(dr_state* state, const dr_predicate* pred, int64_t** selected, int
  * column 0, for what a predicate column of that source is refused for, and for DR_SRC_PARTITION. */
 int dr_state_stats_column(dr_state* state, const char* name, int32_t type_with_source, int64_t** values,
                           uint8_t** isnull, int64_t* n);
+
+/* Metadata-only aggregates (an addition within ABI 4): COUNT / MIN / MAX / SUM of up to 16 inputs over a
+ * selection of the live side, per group, reduced on the device (k_agg.hip) -- the answer is a few bytes
+ * a group instead of a column. What count(*), max(partition column), min / max(id) from minValues /
+ * maxValues and DeltaScan's three DataSize(bytesCompressed, rows) read (D/stats/DeltaScan.scala:29-52).
+ *
+ * Selection: `rows` holds live export positions (the numbering of dr_filter, dr_state_export_rows and
+ * dr_state_partition_groups' order), in any order, repeats allowed (a repeat counts twice); rows == NULL
+ * is every live file in export order (nrows is then ignored). Groups: group_off == NULL is one group
+ * over the whole selection (ngroups is then ignored and 1); else group_off has ngroups + 1 entries,
+ * group_off[0] == 0, non-decreasing, the last one the selection's size, and group g is selection
+ * positions [group_off[g], group_off[g + 1]) -- empty groups are legal, and the (order, group_off) pair
+ * of dr_state_partition_groups plugs in unchanged.
+ *
+ * A spec's input is a K5 cache column (DR_AGG_IN_COLUMN: `name` and `type_with_source` as a predicate
+ * column's, partition values or DR_SRC_STATS_*; built on first use and cached with dr_filter's) or the
+ * AddFile's size / modificationTime (never NULL; name "" and type 0). NULL inputs are skipped.
+ *   DR_AGG_COUNT  nonnull is the answer; value_lo = value_hi = 0.
+ *   DR_AGG_SUM    over BYTE .. LONG columns (nullCount and numRecords are LONG), size and
+ *                 modificationTime: the exact 128-bit two's-complement sum, low word in value_lo, high
+ *                 word in value_hi (Spark's non-ANSI sum(long) is value_lo; it overflowed when
+ *                 value_hi != value_lo >> 63). No non-NULL input: 0.
+ *   DR_AGG_MIN / DR_AGG_MAX  over every type a K5 cache column holds. value_lo: the integer kinds, DATE
+ *                 days and TIMESTAMP micros sign-extended (value_hi = value_lo >> 63), BOOLEAN 0 / 1,
+ *                 FLOAT bits zero-extended and DOUBLE bits (value_hi = 0) in dr_filter's order
+ *                 (SQLOrderingUtil: -0.0 = 0.0, NaN = NaN, NaN above +Infinity); DECIMAL the 128-bit
+ *                 unscaled value in value_lo / value_hi. STRING / BINARY compare as unsigned bytes, a
+ *                 proper prefix first; the winner's bytes are str_bytes[str_off[c] .. str_off[c + 1])
+ *                 of cell c = a * ngroups + g (value_lo = value_hi = 0). arg_row is the live export
+ *                 position that attains the value. Values equal under the order (the same value in
+ *                 several files, -0.0 and 0.0) go to the earliest selection position of the group: the
+ *                 value is that row's own bits. No non-NULL input: value 0 / empty, arg_row = -1.
+ * The result does not depend on how the device cut the work or in which order its workgroups ran.
+ *
+ * *out's arrays live in one host block owned by *handle until dr_agg_release (a second release is
+ * DR_E_INVALID_ARG); the handle outlives the state and the context. naggs == 0 is valid and gives
+ * group_rows only. DR_E_INVALID_ARG, before any device work and with the state left usable, naming the
+ * first offending spec or position: aggs == NULL with naggs > 0, naggs outside 0..16, nrows < 0,
+ * ngroups < 0, a rows[i] outside the side, a group_off that breaks the rules above, an unknown fn or
+ * input, a name or type on a built-in input, SUM of another type, and what a predicate column is refused
+ * for (with its texts, the spec index in the column's place). DR_E_UNSUPPORTED for a sharded state, as
+ * dr_state_lookup_paths: a rank's rows are not the table's. */
+enum dr_agg_fn    { DR_AGG_COUNT = 0, DR_AGG_MIN = 1, DR_AGG_MAX = 2, DR_AGG_SUM = 3 };
+enum dr_agg_input { DR_AGG_IN_COLUMN = 0, DR_AGG_IN_SIZE = 1, DR_AGG_IN_MTIME = 2 };
+#define DR_AGG_MAX_SPECS 16
+typedef struct dr_agg_spec {
+  int32_t fn;               /* dr_agg_fn */
+  int32_t input;            /* dr_agg_input */
+  const char* name;         /* IN_COLUMN: as a predicate column's name; else "" */
+  int32_t type_with_source; /* IN_COLUMN: as a predicate column's type (DR_SRC_PARTITION or DR_SRC_STATS_*); else 0 */
+} dr_agg_spec;
+typedef struct dr_agg_result {
+  int64_t ngroups; int32_t naggs;
+  const int64_t* group_rows;   /* [ngroups] selection positions in the group (count of files) */
+  /* the rest indexed [a * ngroups + g] */
+  const int64_t* nonnull;      /* inputs that were not NULL */
+  const int64_t* value_lo;
+  const int64_t* value_hi;
+  const int64_t* arg_row;      /* MIN / MAX: the live export position that attains it, -1 when nonnull == 0; else -1 */
+  const int64_t* str_off;      /* [naggs * ngroups + 1] into str_bytes: STRING / BINARY MIN / MAX values; empty for every other cell */
+  const uint8_t* str_bytes;
+} dr_agg_result;
+typedef struct dr_agg dr_agg;
+int dr_state_aggregate(dr_state* state, const int64_t* rows, int64_t nrows, const int64_t* group_off, int64_t ngroups,
+                       const dr_agg_spec* aggs, int32_t naggs, dr_agg** handle, dr_agg_result* out);
+int dr_agg_release(dr_agg* handle);
 void dr_free(void* p);
 
 /* ---- checkpoint writer --------------------------------------------------
