@@ -144,18 +144,25 @@ def _written_rows():
     return frames, "".join(T.run(f).decode() for f in frames)
 
 
-def _steered_table(table):
+def _rows(n, shown):
+    """{valid add row: its add.stats} of this file's table."""
+    assert n > FAR_ROW + 1000
+    return {0: MARKER, n - 1: MARKER,
+            1: _low_bytes_ascii('{"tags":"', "Z" * 65616, '"}'),
+            2: '{"tags":"%s"}' % "".join(_random(6, 50 + p) + run for p, run in _period_runs()),
+            3: '{"tags":"%s"}' % _written_rows()[1],
+            FAR_ROW: _low_bytes_ascii('{"tags":"' + STRETCH, "Z" * 65616, '"}')}
+
+
+def _steered_table(table, rows_of, shown):
+    """The table with add.stats steered: rows_of(number of valid add rows, shown) -> {row: value}; the other rows are
+    fillers. shown[i]: the live state takes valid row i's stats from the checkpoint."""
     import pyarrow as pa
     col = table.schema.get_field_index("add")
     add = table.column(col).combine_chunks()
     valid = add.is_valid().to_pylist()
     n = sum(valid)
-    assert n > FAR_ROW + 1000
-    rows = {0: MARKER, n - 1: MARKER,
-            1: _low_bytes_ascii('{"tags":"', "Z" * 65616, '"}'),
-            2: '{"tags":"%s"}' % "".join(_random(6, 50 + p) + run for p, run in _period_runs()),
-            3: '{"tags":"%s"}' % _written_rows()[1],
-            FAR_ROW: _low_bytes_ascii('{"tags":"' + STRETCH, "Z" * 65616, '"}')}
+    rows = rows_of(n, shown)
     it = iter(range(n))
     stats = pa.array([(lambda i: rows.get(i, FILL % i))(next(it)) if v else None for v in valid], pa.string())
     k = add.type.get_field_index("stats")
@@ -641,7 +648,7 @@ def engine():
     return Engine.get(0)
 
 
-def build_base(d):
+def build_base(d, rows_of=_rows):
     """(the SNAPPY twin's log, the checkpoint's name, the steered table, cutoff, the oracle's snapshot, the original
     table): everything the bodies need, without a device."""
     import pyarrow.parquet as pq
@@ -651,10 +658,14 @@ def build_base(d):
     ck = [f for f in os.listdir(lp) if f.endswith(".checkpoint.parquet")]
     assert len(ck) == 1
     original = pq.read_table(os.path.join(lp, ck[0]))
-    table = _steered_table(original)
+    cutoff = exp.min_file_retention_timestamp
+    live = {a["path"]: a.get("stats") for a in O.state_reconstruction(O.get_log_segment(lp), cutoff).all_files}
+    add = original.column("add").combine_chunks()
+    shown = [p in live and live[p] == s for p, s, v in zip(add.field("path").to_pylist(), add.field("stats").to_pylist(),
+                                                            add.is_valid().to_pylist()) if v]
+    table = _steered_table(original, rows_of, shown)
     pq.write_table(table, os.path.join(lp, ck[0]), compression="snappy", use_dictionary=False, version="1.0",
                    write_statistics=False)
-    cutoff = exp.min_file_retention_timestamp
     return lp, ck[0], table, cutoff, O.state_reconstruction(O.get_log_segment(lp), cutoff), original
 
 
