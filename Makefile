@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := delta_amd/csrc
 LIB := delta_amd/libdeltareplay.so
-HIP_SRCS := $(CSRC)/engine.hip $(CSRC)/k_json.hip $(CSRC)/k_parquet.hip $(CSRC)/k_snappy.hip $(CSRC)/k_inflate.hip $(CSRC)/k_zstd.hip $(CSRC)/k_lz4.hip $(CSRC)/k_replay.hip $(CSRC)/k_util.hip $(CSRC)/k_shard.hip $(CSRC)/k_filter.hip $(CSRC)/k_index.hip $(CSRC)/k_encode.hip $(CSRC)/k_rows.hip $(CSRC)/k_lookup.hip $(CSRC)/k_agg.hip
+HIP_SRCS := $(CSRC)/engine.hip $(CSRC)/k_json.hip $(CSRC)/k_parquet.hip $(CSRC)/k_snappy.hip $(CSRC)/k_inflate.hip $(CSRC)/k_zstd.hip $(CSRC)/k_lz4.hip $(CSRC)/k_replay.hip $(CSRC)/k_util.hip $(CSRC)/k_shard.hip $(CSRC)/k_filter.hip $(CSRC)/k_index.hip $(CSRC)/k_encode.hip $(CSRC)/k_rows.hip $(CSRC)/k_lookup.hip $(CSRC)/k_agg.hip $(CSRC)/k_probe.hip
 CXX_SRCS := $(CSRC)/parquet_meta.cpp $(CSRC)/log_segment.cpp $(CSRC)/json_host.cpp $(CSRC)/snappy_host.cpp $(CSRC)/inflate_host.cpp $(CSRC)/zstd_host.cpp $(CSRC)/lz4_host.cpp $(CSRC)/pred_plan.cpp
 OBJDIR := build/obj
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))

@@ -32,7 +32,7 @@ DR_FLAG_REDUCE64 = 0x4
 ABI_VERSION = 4  # include/deltareplay.h DR_ABI_VERSION
 # context options (include/deltareplay.h enum dr_option)
 OPTIONS = {"overlap": 1, "split": 2, "bucket_bits": 3, "filter_eval": 4, "apply_full": 5, "canon_hint": 6,
-           "json_staged": 7, "host_cache_bytes": 8, "lookup_key_bits": 9}
+           "json_staged": 7, "host_cache_bytes": 8, "lookup_key_bits": 9, "probe_search": 10}
 DR_LOOKUP_ABSENT, DR_LOOKUP_LIVE, DR_LOOKUP_TOMBSTONE = 0, 1, 2  # enum dr_lookup_hit
 
 # Exported symbols (checked by tests/test_native_abi.py against include/deltareplay.h).
@@ -44,7 +44,7 @@ SYMBOLS = [
     "dr_replay_sharded", "dr_staged_release", "dr_staged_bytes", "dr_staged_plan",
     "dr_replay_staged",
     "dr_replay", "dr_state_release", "dr_state_apply", "dr_state_counts", "dr_state_local_counts", "dr_state_nonfile_json", "dr_state_check_checksum",
-    "dr_state_export", "dr_state_export_plan", "dr_state_export_range", "dr_state_export_rows", "dr_state_lookup_paths", "dr_range_release", "dr_state_materialize", "dr_state_record_sums", "dr_state_record_hashes", "dr_state_write_checkpoint", "dr_state_set_nonfile_json", "dr_filter", "dr_state_stats_column", "dr_state_aggregate", "dr_agg_release", "dr_state_scan_order", "dr_state_partition_groups", "dr_free", "dr_last_timings", "dr_set_timing", "dr_set_timing_only",
+    "dr_state_export", "dr_state_export_plan", "dr_state_export_range", "dr_state_export_rows", "dr_state_lookup_paths", "dr_range_release", "dr_state_materialize", "dr_state_record_sums", "dr_state_record_hashes", "dr_state_write_checkpoint", "dr_state_set_nonfile_json", "dr_filter", "dr_state_stats_column", "dr_state_aggregate", "dr_agg_release", "dr_state_probe_keys", "dr_probe_release", "dr_state_scan_order", "dr_state_partition_groups", "dr_free", "dr_last_timings", "dr_set_timing", "dr_set_timing_only",
     "dr_shard_plan", "dr_stage_log_shard", "dr_shard_begin", "dr_shard_pack", "dr_shard_reduce",
     "dr_shard_finish", "dr_shard_release", "dr_parse_commits", "dr_parsed_release",
 ]
@@ -57,8 +57,11 @@ DR_AGG_COUNT, DR_AGG_MIN, DR_AGG_MAX, DR_AGG_SUM = 0, 1, 2, 3
 DR_AGG_IN_COLUMN, DR_AGG_IN_SIZE, DR_AGG_IN_MTIME = 0, 1, 2
 DR_AGG_MAX_SPECS = 16
 AGG_TILE = 1024  # selection positions per workgroup of k_agg_tiles (delta_amd/csrc/kernels.h AGG_TILE)
+# dr_state_probe_keys (delta_amd/csrc/kernels.h): threads of a workgroup, workgroups of k_probe_files at most
+# (a longer selection is strided), splitter table entries in LDS at most
+PROBE_BLOCK, PROBE_GRID, PROBE_TAB = 256, 1024, 4096
 # additions within ABI 4 that a library from before lacks: looked up, and done without when absent
-OPTIONAL_SYMBOLS = ("dr_state_stats_column", "dr_state_aggregate", "dr_agg_release")
+OPTIONAL_SYMBOLS = ("dr_state_stats_column", "dr_state_aggregate", "dr_agg_release", "dr_state_probe_keys", "dr_probe_release")
 
 
 class dr_file(C.Structure):
@@ -122,6 +125,11 @@ class dr_agg_result(C.Structure):
     _fields_ = [("ngroups", C.c_int64), ("naggs", C.c_int32),
                 ("group_rows", _P64), ("nonnull", _P64), ("value_lo", _P64), ("value_hi", _P64),
                 ("arg_row", _P64), ("str_off", _P64), ("str_bytes", _PU8)]
+
+
+class dr_probe_result(C.Structure):
+    _fields_ = [("nselected", C.c_int64), ("selected", _P64), ("hits", _P64), ("unknown", C.c_int64),
+                ("nkeys", C.c_int64), ("key_files", _P64)]
 
 
 def hip_runtimes() -> list:
@@ -194,6 +202,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dr_state_aggregate": ([vp, _P64, i64, _P64, i64, C.POINTER(dr_agg_spec), i32, C.POINTER(vp),
                                 C.POINTER(dr_agg_result)], C.c_int),
         "dr_agg_release": ([vp], C.c_int),
+        "dr_state_probe_keys": ([vp, _P64, i64, C.c_char_p, i32, C.c_char_p, i32, _P64, C.POINTER(C.c_uint8), i64,
+                                 C.c_uint32, C.POINTER(vp), C.POINTER(dr_probe_result)], C.c_int),
+        "dr_probe_release": ([vp], C.c_int),
         "dr_state_write_checkpoint": ([vp, i32, i32, C.c_uint32, C.c_uint64, C.POINTER(C.POINTER(C.c_uint8)),
                                        C.POINTER(C.c_uint64), _P64, _P64], C.c_int),
         "dr_state_scan_order": ([vp, C.POINTER(_P64), _P64], C.c_int),
@@ -232,6 +243,11 @@ def has_stats_sources(lib: C.CDLL) -> bool:
 def has_aggregate(lib: C.CDLL) -> bool:
     """The library reduces on the device (dr_state_aggregate / dr_agg_release, added within ABI 4)."""
     return hasattr(lib, "dr_state_aggregate") and hasattr(lib, "dr_agg_release")
+
+
+def has_probe_keys(lib: C.CDLL) -> bool:
+    """The library probes key sets on the device (dr_state_probe_keys / dr_probe_release, added within ABI 4)."""
+    return hasattr(lib, "dr_state_probe_keys") and hasattr(lib, "dr_probe_release")
 
 
 _LIB = None

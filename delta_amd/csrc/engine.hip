@@ -134,6 +134,7 @@ struct dr_ctx {
     int64_t json_staged = 0;   // DR_OPT_JSON_STAGED: every segment through the staged K1 kernel
     int64_t host_cache_bytes = int64_t(64) << 30;  // DR_OPT_HOST_CACHE_BYTES: pinned blocks kept for reuse
     int64_t lookup_key_bits = 64;  // DR_OPT_LOOKUP_KEY_BITS: key bits the path index keeps (test hook)
+    int64_t probe_search = 0;  // DR_OPT_PROBE_SEARCH: 0 splitter table in LDS + one segment, 1 plain global bisection (test hook)
   } opt;
   // Every entry point that takes this context (or a state, range, shard or communicator of it) holds
   // this lock for the call: a context may be shared by host threads (several Spark tasks of one
@@ -5676,6 +5677,7 @@ static int64_t* option_slot(dr_ctx* ctx, int32_t option) {
     case DR_OPT_JSON_STAGED: return &o.json_staged;
     case DR_OPT_HOST_CACHE_BYTES: return &o.host_cache_bytes;
     case DR_OPT_LOOKUP_KEY_BITS: return &o.lookup_key_bits;
+    case DR_OPT_PROBE_SEARCH: return &o.probe_search;
     default: return nullptr;
   }
 }
@@ -5686,7 +5688,7 @@ int dr_ctx_set_option(dr_ctx* ctx, int32_t option, int64_t value) {
   int64_t* v = option_slot(ctx, option);
   bool ok = v != nullptr;
   switch (option) {  // the accepted values (include/deltareplay.h)
-    case DR_OPT_OVERLAP: case DR_OPT_SPLIT: case DR_OPT_APPLY_FULL: case DR_OPT_JSON_STAGED:
+    case DR_OPT_OVERLAP: case DR_OPT_SPLIT: case DR_OPT_APPLY_FULL: case DR_OPT_JSON_STAGED: case DR_OPT_PROBE_SEARCH:
       ok = value == 0 || value == 1;
       break;
     case DR_OPT_BUCKET_BITS: ok = value >= -1 && value <= 32; break;
@@ -6818,6 +6820,179 @@ int dr_agg_release(dr_agg* handle) {
   if (!handle) return DR_OK;
   std::lock_guard<std::mutex> g(g_aggs_mu);
   if (!g_aggs.erase(handle)) return DR_E_INVALID_ARG;  // not a live handle (released twice)
+  delete handle;
+  return DR_OK;
+}
+
+// dr_state_probe_keys' result: one host block, registered like a dr_agg so that it outlives its state
+// and context and a second release is refused.
+struct dr_probe {
+  std::vector<int64_t> words;   // selected, hits, key_files
+};
+static std::mutex g_probes_mu;
+static std::unordered_set<dr_probe*> g_probes;
+
+// The probe of the selection's [lo, hi] ranges against the keys (k_probe.hip). The arguments have passed
+// check_probe_args and check_probe_rows. Up go 8 B a key (9 with a null mask) and 8 B a given row; down
+// come 16 B a selected position and 8 B a key; the bounds' columns stay where the K5 cache holds them.
+// Every temporary is a buffer of this call.
+static void probe_state(dr_state& st, const int64_t* rows, uint64_t n, const char* lo_name, int32_t lo_type,
+                        const char* hi_name, int32_t hi_type, const int64_t* keys, const uint8_t* key_null, uint64_t nkeys,
+                        dr_probe& R, dr_probe_result* out) {
+  DR_STAGE("probe_keys", st.ctx->stream);
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  std::vector<int64_t> sel, sel_hits, key_files(nkeys, 0);
+  if (n) {
+    auto find = [&](const std::string& name, int32_t type) -> dr_state::PvCol* {
+      for (auto& c : st.pv_cols)
+        if (c->name == name && c->type == type) return c.get();
+      return nullptr;
+    };
+    // the two bounds in the K5 cache (built when not there yet, by source as dr_filter does)
+    std::vector<std::pair<std::string, int32_t>> want, want_stats;
+    for (const auto& k : {std::pair<std::string, int32_t>{lo_name, lo_type}, std::pair<std::string, int32_t>{hi_name, hi_type}}) {
+      auto& into = (k.second & DR_SRC_MASK) ? want_stats : want;
+      if (!find(k.first, k.second) && std::find(into.begin(), into.end(), k) == into.end()) into.push_back(k);
+    }
+    if (!want.empty()) build_pv_columns(st, want);
+    if (!want_stats.empty()) build_stats_columns(st, want_stats);
+    const dr_state::PvCol* lo = find(lo_name, lo_type);
+    const dr_state::PvCol* hi = find(hi_name, hi_type);
+    if (!lo || !hi) fail(DR_E_INTERNAL, "probe_keys: a cache column was not built");
+    const int32_t base = lo_type & 0xff;
+    ProbeArgs A{};
+    A.n = n;
+    A.base = base;
+    A.wide = base == DR_T_LONG || base == DR_T_TIMESTAMP || base == DR_T_DOUBLE;
+    A.lo_v = A.wide ? static_cast<const void*>(lo->w64.p) : static_cast<const void*>(lo->w32.p);
+    A.hi_v = A.wide ? static_cast<const void*>(hi->w64.p) : static_cast<const void*>(hi->w32.p);
+    A.lo_null = lo->isnull.p;
+    A.hi_null = hi->isnull.p;
+    if (!A.lo_v || !A.hi_v || !A.lo_null || !A.hi_null) fail(DR_E_INTERNAL, "probe_keys: a cache column lacks its values");
+    A.lo_stats = (lo_type & DR_SRC_MASK) != 0;
+    A.hi_stats = (hi_type & DR_SRC_MASK) != 0;
+
+    // the keys: order keys beside caller indices without the NULL ones, sorted, de-duplicated
+    DBuf<uint8_t> scratch(ctx, scan_scratch_for(std::max<uint64_t>(n, nkeys) + 1));
+    DBuf<uint32_t> slot_of(ctx, nkeys);
+    DBuf<int64_t> dkeys(ctx, nkeys);
+    uint64_t ndist = 0;
+    if (nkeys) {
+      DBuf<int64_t> d_keys = upload(ctx, keys, nkeys);
+      DBuf<uint8_t> d_null;
+      DBuf<uint64_t> kpos;
+      uint64_t m = nkeys;
+      if (key_null) {
+        d_null = upload(ctx, key_null, nkeys);
+        DBuf<uint32_t> kflag(ctx, nkeys);
+        kpos = DBuf<uint64_t>(ctx, nkeys + 1);
+        launch_probe_key_flags(d_null.p, nkeys, kflag.p, stream);
+        launch_scan_u32(kflag.p, kpos.p, nkeys, ss(scratch), stream);
+        m = d2h_one(kpos.p + nkeys, stream);
+      }
+      HIP_OK(hipMemsetAsync(slot_of.p, 0xff, nkeys * sizeof(uint32_t), stream));  // PROBE_NO_SLOT
+      if (m) {
+        DBuf<int64_t> enc(ctx, nkeys), sorted(ctx, m);
+        DBuf<uint32_t> idx(ctx, nkeys), sidx(ctx, m), head(ctx, m);
+        DBuf<uint64_t> hpos(ctx, m + 1);
+        launch_probe_keys_prepare(d_keys.p, key_null ? d_null.p : nullptr, key_null ? kpos.p : nullptr, nkeys, base, enc.p,
+                                  idx.p, stream);
+        size_t tb = 0;
+        launch_probe_sort(nullptr, &tb, enc.p, sorted.p, idx.p, sidx.p, m, stream);
+        DBuf<uint8_t> temp(ctx, tb);
+        launch_probe_sort(temp.p, &tb, enc.p, sorted.p, idx.p, sidx.p, m, stream);
+        launch_probe_key_heads(sorted.p, m, head.p, stream);
+        launch_scan_u32(head.p, hpos.p, m, ss(scratch), stream);
+        ndist = d2h_one(hpos.p + m, stream);
+        launch_probe_key_compact(sorted.p, sidx.p, head.p, hpos.p, m, dkeys.p, slot_of.p, stream);
+      }
+    }
+    A.dkeys = dkeys.p;
+    A.ndist = uint32_t(ndist);
+    A.seg = probe_seg(A.ndist);
+    A.ntab = probe_ntab(A.ndist);
+
+    // the files
+    DBuf<int64_t> d_rows;
+    if (rows) d_rows = upload(ctx, rows, n);
+    A.rows = rows ? d_rows.p : nullptr;
+    DBuf<int64_t> hits(ctx, n);
+    DBuf<uint32_t> flag(ctx, n), counters(ctx, 2 * (ndist + 1));
+    counters.zero(stream);
+    A.hits = hits.p;
+    A.flag = flag.p;
+    A.start = counters.p;
+    A.end = counters.p + ndist + 1;
+    launch_probe_files(A, ctx->opt.probe_search == 1, stream);
+    DBuf<uint64_t> pos(ctx, n + 1);
+    launch_scan_u32(flag.p, pos.p, n, ss(scratch), stream);
+    const uint64_t nsel = d2h_one(pos.p + n, stream);
+    DBuf<int64_t> d_sel(ctx, 2 * nsel);
+    launch_probe_select(A, pos.p, d_sel.p, d_sel.p + nsel, stream);
+    if (nkeys) {
+      DBuf<uint64_t> s_scan(ctx, ndist + 2), e_scan(ctx, ndist + 2);
+      DBuf<int64_t> d_kf(ctx, nkeys);
+      launch_scan_u32(A.start, s_scan.p, ndist + 1, ss(scratch), stream);
+      launch_scan_u32(A.end, e_scan.p, ndist + 1, ss(scratch), stream);
+      launch_probe_key_files(slot_of.p, s_scan.p, e_scan.p, nkeys, d_kf.p, stream);
+      key_files = d2h(d_kf.p, nkeys, stream);
+    }
+    sel = d2h(d_sel.p, nsel, stream);
+    sel_hits = d2h(d_sel.p + nsel, nsel, stream);
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+  ctx->collect_timings();
+  const size_t nsel = sel.size();
+  R.words.resize(2 * nsel + nkeys + 1);
+  std::copy(sel.begin(), sel.end(), R.words.begin());
+  std::copy(sel_hits.begin(), sel_hits.end(), R.words.begin() + nsel);
+  std::copy(key_files.begin(), key_files.end(), R.words.begin() + 2 * nsel);
+  out->nselected = int64_t(nsel);
+  out->selected = R.words.data();
+  out->hits = R.words.data() + nsel;
+  out->unknown = int64_t(std::count(sel_hits.begin(), sel_hits.end(), int64_t(-1)));
+  out->nkeys = int64_t(nkeys);
+  out->key_files = R.words.data() + 2 * nsel;
+}
+
+int dr_state_probe_keys(dr_state* state, const int64_t* rows, int64_t nrows, const char* lo_name, int32_t lo_type,
+                        const char* hi_name, int32_t hi_type, const int64_t* keys, const uint8_t* key_null, int64_t nkeys,
+                        uint32_t flags, dr_probe** handle, dr_probe_result* out) {
+  if (!state || !handle || !out) return DR_E_INVALID_ARG;
+  *handle = nullptr;
+  memset(out, 0, sizeof(*out));
+  dr_ctx* ctx = state->ctx;
+  const int rc = guard(ctx, [&] {
+    // the arguments first: nothing is built, staged or read through them before they hold
+    check_probe_args(rows != nullptr, nrows, lo_name, lo_type, hi_name, hi_type, keys, nkeys, flags);
+    if (state->sharded)
+      fail(DR_E_UNSUPPORTED, "dr_state_probe_keys: a sharded state holds this rank's source-side survivors only; "
+                             "a rank-local answer would mislead");
+    HIP_OK(hipSetDevice(ctx->device));
+    ctx->begin_call();
+    ensure_ready(*state);  // the side's size, which the selection is checked against
+    if (state->sources.empty()) fail(DR_E_INVALID_ARG, "state has no staged segment");
+    check_probe_rows(rows, nrows, state->n_live);
+    auto R = std::make_unique<dr_probe>();
+    probe_state(*state, rows, rows ? uint64_t(nrows) : state->n_live, lo_name, lo_type, hi_name, hi_type, keys, key_null,
+                uint64_t(nkeys), *R, out);
+    std::lock_guard<std::mutex> g(g_probes_mu);
+    g_probes.insert(R.get());
+    *handle = R.release();
+  });
+  if (rc != DR_OK) {
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::recursive_mutex> g(ctx->api_mu);
+    ctx->drop_timings();
+  }
+  return rc;
+}
+
+int dr_probe_release(dr_probe* handle) {
+  if (!handle) return DR_OK;
+  std::lock_guard<std::mutex> g(g_probes_mu);
+  if (!g_probes.erase(handle)) return DR_E_INVALID_ARG;  // not a live handle (released twice)
   delete handle;
   return DR_OK;
 }

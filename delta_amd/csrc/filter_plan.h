@@ -61,6 +61,16 @@ DR_HD inline int64_t fp_key_widen(int64_t k32) {
   }
   return fp_key64(d);
 }
+// dr_state_probe_keys: a word in dr_state_stats_column's encoding (a caller's key, a bound widened from
+// its cache column) as the int64 the probe sorts, de-duplicates and searches by. FLOAT (the low 32 bits)
+// and DOUBLE go through their order keys, so -0.0 and 0.0 are one key and every NaN is the one value
+// above +Infinity; every other supported type is a signed integer already. Host (tests) and device
+// (k_probe.hip) both call this.
+DR_HD inline int64_t probe_order_key(int32_t base, int64_t word) {
+  if (base == 7 /* DR_T_FLOAT */) return fp_key32(uint32_t(uint64_t(word)));
+  if (base == 8 /* DR_T_DOUBLE */) return fp_key64(uint64_t(word));
+  return word;
+}
 // The kind a leaf evaluates a column as: BINARY as STRING (bytes), TIMESTAMP as LONG (one 64-bit
 // integer); FLOAT / DOUBLE through their keys; DECIMAL as two words (w64 unsigned under w64hi).
 DR_HD inline int32_t leaf_kind(int32_t type) {

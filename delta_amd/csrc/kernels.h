@@ -1050,3 +1050,52 @@ void launch_agg_combine(const AggArgs& a, hipStream_t st);
 void launch_agg_str_len(const AggArgs& a, uint32_t* len, hipStream_t st);
 void launch_agg_str_copy(const AggArgs& a, const uint64_t* off, uint8_t* bytes, hipStream_t st);
 }  // namespace dr
+
+// ---- key probe (k_probe.hip, dr_state_probe_keys) ----------------------------------------------------
+namespace dr {
+constexpr uint32_t PROBE_BLOCK = 256;    // threads of a workgroup of every kernel here
+constexpr uint32_t PROBE_GRID = 1024;    // workgroups of k_probe_files at most: 4 per CU; a longer selection is strided
+constexpr uint32_t PROBE_TAB = 4096;     // splitter table entries in LDS at most (32 KiB: four workgroups per CU)
+constexpr uint32_t PROBE_NO_SLOT = 0xffffffffu;  // a NULL key's entry of the caller-index -> distinct-slot map
+// The splitter table samples every seg-th distinct key, the first of each segment: seg = 1 while the
+// keys fit the table (the search then never leaves LDS), else the least length that fits.
+inline uint32_t probe_seg(uint32_t ndist) { return ndist <= PROBE_TAB ? 1u : (ndist + PROBE_TAB - 1) / PROBE_TAB; }
+inline uint32_t probe_ntab(uint32_t ndist) { return ndist ? (ndist + probe_seg(ndist) - 1) / probe_seg(ndist) : 0u; }
+struct ProbeArgs {
+  const int64_t* rows;      // [n] live export positions; null pointer: position p is row p
+  uint64_t n;               // selection size
+  int32_t base;             // DR_T_* of both bounds
+  int32_t wide;             // 1: the bounds' values are w64 columns, 0: w32
+  const void* lo_v;
+  const void* hi_v;
+  const uint8_t* lo_null;
+  const uint8_t* hi_null;
+  int32_t lo_stats, hi_stats;  // the bound comes from a statistics source: NULL means "unknown", not "no match"
+  const int64_t* dkeys;     // [ndist] distinct order keys, ascending
+  uint32_t ndist, seg, ntab;
+  int64_t* hits;            // [n] distinct keys within [lo, hi]; -1 unknown
+  uint32_t* flag;           // [n] 1: selected
+  uint32_t* start;          // [ndist + 1] zeroed: known positions whose first key is slot a
+  uint32_t* end;            // [ndist + 1] zeroed: known positions whose range ends before slot b
+};
+// Keys: the non-NULL ones as (order key, caller index) pairs, packed in caller order (pos: the exclusive
+// scan of the non-NULL flags, a null pointer when no key is NULL); sorted by order key; run heads marked;
+// the distinct keys compacted and every caller index mapped to its distinct slot.
+void launch_probe_key_flags(const uint8_t* key_null, uint64_t n, uint32_t* flag, hipStream_t st);
+void launch_probe_keys_prepare(const int64_t* keys, const uint8_t* key_null, const uint64_t* pos, uint64_t n, int32_t base,
+                               int64_t* enc, uint32_t* idx, hipStream_t st);
+void launch_probe_sort(void* temp, size_t* temp_bytes, const int64_t* k_in, int64_t* k_out, const uint32_t* v_in,
+                       uint32_t* v_out, uint64_t m, hipStream_t st);
+void launch_probe_key_heads(const int64_t* sorted, uint64_t m, uint32_t* head, hipStream_t st);
+void launch_probe_key_compact(const int64_t* sorted, const uint32_t* idx, const uint32_t* head, const uint64_t* hpos,
+                              uint64_t m, int64_t* dkeys, uint32_t* slot_of, hipStream_t st);
+// The hot kernel: one lane per selection position, lower_bound(lo) and upper_bound(hi) over the distinct
+// keys; plain = the comparison variant that searches global memory only (DR_OPT_PROBE_SEARCH = 1).
+void launch_probe_files(const ProbeArgs& a, bool plain, hipStream_t st);
+// Selected positions in selection order: rows[p] (or p) and hits[p] to pos[p] where flag[p].
+void launch_probe_select(const ProbeArgs& a, const uint64_t* pos, int64_t* sel, int64_t* sel_hits, hipStream_t st);
+// key_files[i] = start_incl[slot] - end_incl[slot] for caller key i's slot (s_scan / e_scan: the exclusive
+// scans of start / end over ndist + 1 entries, so the inclusive sum at j is entry j + 1); a NULL key: 0.
+void launch_probe_key_files(const uint32_t* slot_of, const uint64_t* s_scan, const uint64_t* e_scan, uint64_t nkeys,
+                            int64_t* key_files, hipStream_t st);
+}  // namespace dr

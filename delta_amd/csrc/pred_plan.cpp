@@ -22,33 +22,39 @@ namespace dr {
 static int32_t col_type(const dr_predicate& p, int32_t c) { return p.col_types[c] & ~int32_t(DR_SRC_MASK); }
 static int32_t col_source(const dr_predicate& p, int32_t c) { return (p.col_types[c] >> DR_SRC_SHIFT) & 0xf; }
 
-void check_column_source(const char* name, int32_t type_with_source, int32_t c) {
+// check_column_source with the column given as text: an index for a predicate column or an aggregate
+// spec, "lo" / "hi" for a bound of dr_state_probe_keys.
+static void check_source_of(const char* name, int32_t type_with_source, const char* c) {
   const int32_t src = (type_with_source >> DR_SRC_SHIFT) & 0xf, base = type_with_source & 0xff;
   if (src == DR_SRC_PARTITION) return;
   if (src > DR_SRC_STATS_NUMRECORDS)
-    fail(DR_E_INVALID_ARG, fmt("predicate column %d: unknown source %d (DR_SRC_PARTITION .. DR_SRC_STATS_NUMRECORDS)", c, src));
+    fail(DR_E_INVALID_ARG, fmt("predicate column %s: unknown source %d (DR_SRC_PARTITION .. DR_SRC_STATS_NUMRECORDS)", c, src));
   if ((src == DR_SRC_STATS_MIN || src == DR_SRC_STATS_MAX) && (base == DR_T_BOOLEAN || base == DR_T_BINARY))
-    fail(DR_E_INVALID_ARG, fmt("predicate column %d: %s statistics have no %s (type %d)", c, src == DR_SRC_STATS_MIN ? "minValues" : "maxValues",
+    fail(DR_E_INVALID_ARG, fmt("predicate column %s: %s statistics have no %s (type %d)", c, src == DR_SRC_STATS_MIN ? "minValues" : "maxValues",
                                base == DR_T_BOOLEAN ? "BOOLEAN" : "BINARY", base));
   if ((src == DR_SRC_STATS_NULLCOUNT || src == DR_SRC_STATS_NUMRECORDS) && (type_with_source & ~int32_t(DR_SRC_MASK)) != DR_T_LONG)
-    fail(DR_E_INVALID_ARG, fmt("predicate column %d: %s is a LONG, not type %d", c, src == DR_SRC_STATS_NULLCOUNT ? "nullCount" : "numRecords",
+    fail(DR_E_INVALID_ARG, fmt("predicate column %s: %s is a LONG, not type %d", c, src == DR_SRC_STATS_NULLCOUNT ? "nullCount" : "numRecords",
                                type_with_source & ~int32_t(DR_SRC_MASK)));
   const size_t len = std::strlen(name);
   if (src == DR_SRC_STATS_NUMRECORDS) {
-    if (len) fail(DR_E_INVALID_ARG, fmt("predicate column %d: numRecords takes the name \"\", not a path of %zu bytes", c, len));
+    if (len) fail(DR_E_INVALID_ARG, fmt("predicate column %s: numRecords takes the name \"\", not a path of %zu bytes", c, len));
     return;
   }
   if (len > size_t(sj::SJ_MAXPATH))
-    fail(DR_E_INVALID_ARG, fmt("predicate column %d: a statistics path has at most %d bytes, not %zu", c, sj::SJ_MAXPATH, len));
+    fail(DR_E_INVALID_ARG, fmt("predicate column %s: a statistics path has at most %d bytes, not %zu", c, sj::SJ_MAXPATH, len));
   int segs = 1;
   for (size_t q = 0; q <= len; ++q) {
     const bool end = q == len || uint8_t(name[q]) == sj::SJ_SEP;
     if (end && (q == 0 || uint8_t(name[q - 1]) == sj::SJ_SEP))
-      fail(DR_E_INVALID_ARG, fmt("predicate column %d: segment %d of the statistics path is empty", c, segs - 1));
+      fail(DR_E_INVALID_ARG, fmt("predicate column %s: segment %d of the statistics path is empty", c, segs - 1));
     if (end && q < len) ++segs;
   }
   if (segs > sj::SJ_MAXSEG)
-    fail(DR_E_INVALID_ARG, fmt("predicate column %d: a statistics path has at most %d segments, not %d", c, sj::SJ_MAXSEG, segs));
+    fail(DR_E_INVALID_ARG, fmt("predicate column %s: a statistics path has at most %d segments, not %d", c, sj::SJ_MAXSEG, segs));
+}
+
+void check_column_source(const char* name, int32_t type_with_source, int32_t c) {
+  check_source_of(name, type_with_source, fmt("%d", c).c_str());
 }
 
 void check_agg_specs(const dr_agg_spec* aggs, int32_t naggs) {
@@ -98,6 +104,44 @@ void check_agg_selection(const int64_t* rows, int64_t nrows, uint64_t side, cons
   if (uint64_t(group_off[ngroups]) != n)
     fail(DR_E_INVALID_ARG, fmt("dr_state_aggregate: group_off[%lld] = %lld, not the selection's %llu rows", (long long)ngroups,
                                (long long)group_off[ngroups], (unsigned long long)n));
+}
+
+// One bound of dr_state_probe_keys: `who` is "lo" or "hi".
+static void check_probe_bound(const char* who, const char* name, int32_t type_with_source) {
+  if (!name) fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: %s needs a name", who));
+  const int32_t t = type_with_source & ~int32_t(DR_SRC_MASK), base = t & 0xff;
+  bool type_ok = type_with_source >= 0 && (base == DR_T_DECIMAL || t <= DR_T_BINARY);
+  if (type_ok && base == DR_T_DECIMAL) {
+    const int32_t prec = (t >> 8) & 0xff, scale = t >> 16;
+    type_ok = prec >= 1 && prec <= 38 && scale <= prec;
+  }
+  if (!type_ok) fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: %s has no valid column type (code %d)", who, type_with_source));
+  if (base == DR_T_STRING || base == DR_T_BINARY || base == DR_T_DECIMAL || base == DR_T_BOOLEAN)
+    fail(DR_E_UNSUPPORTED, fmt("dr_state_probe_keys: %s is of type %d; STRING, BINARY, DECIMAL and BOOLEAN bounds are not probed", who, base));
+  check_source_of(name, type_with_source, who);
+}
+
+void check_probe_args(bool has_rows, int64_t nrows, const char* lo_name, int32_t lo_type, const char* hi_name,
+                      int32_t hi_type, const int64_t* keys, int64_t nkeys, uint32_t flags) {
+  if (flags != 0) fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: flags = %u, not 0", flags));
+  if (has_rows && nrows < 0) fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: nrows = %lld is negative", (long long)nrows));
+  if (has_rows && nrows > int64_t(UINT32_MAX))  // the kernel counts a key's files in 32 bits
+    fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: nrows = %lld is above %u", (long long)nrows, UINT32_MAX));
+  if (nkeys < 0 || nkeys > int64_t(INT32_MAX))
+    fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: nkeys = %lld is outside 0..%d", (long long)nkeys, INT32_MAX));
+  if (nkeys && !keys) fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: keys == NULL with nkeys = %lld", (long long)nkeys));
+  check_probe_bound("lo", lo_name, lo_type);
+  check_probe_bound("hi", hi_name, hi_type);
+  if ((lo_type & 0xff) != (hi_type & 0xff))
+    fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: lo is of type %d and hi of type %d; both bounds take one base type",
+                               lo_type & 0xff, hi_type & 0xff));
+}
+
+void check_probe_rows(const int64_t* rows, int64_t nrows, uint64_t side) {
+  for (int64_t i = 0; rows && i < nrows; ++i)
+    if (rows[i] < 0 || uint64_t(rows[i]) >= side)
+      fail(DR_E_INVALID_ARG, fmt("dr_state_probe_keys: rows[%lld] = %lld is outside [0, %llu)", (long long)i, (long long)rows[i],
+                                 (unsigned long long)side));
 }
 
 static bool new_pred_type(int32_t t) { return (t & 0xff) >= DR_T_FLOAT; }

@@ -29,6 +29,17 @@ void check_column_source(const char* name, int32_t type_with_source, int32_t c);
 void check_agg_specs(const dr_agg_spec* aggs, int32_t naggs);
 void check_agg_selection(const int64_t* rows, int64_t nrows, uint64_t side, const int64_t* group_off, int64_t ngroups);
 
+// dr_state_probe_keys' host checks, in this order, each naming the first offender. check_probe_args:
+// flags == 0, nrows in 0..2^32 - 1 where rows are given (a key's files are counted in 32 bits), nkeys in 0..2^31 - 1, keys where nkeys > 0, then per bound
+// ("lo", then "hi") a name, a valid type code, a supported base type (STRING, BINARY, DECIMAL and BOOLEAN:
+// DR_E_UNSUPPORTED) and what check_column_source asks (its texts, "lo" / "hi" in the column's place), and
+// last one base type for both. check_probe_rows: rows within a side of `side` files. Everything but the
+// unsupported types is DR_E_INVALID_ARG. The order map the probe compares by is filter_plan.h's
+// probe_order_key.
+void check_probe_args(bool has_rows, int64_t nrows, const char* lo_name, int32_t lo_type, const char* hi_name,
+                      int32_t hi_type, const int64_t* keys, int64_t nkeys, uint32_t flags);
+void check_probe_rows(const int64_t* rows, int64_t nrows, uint64_t side);
+
 // Literal k as the evaluators compare it: FLOAT / DOUBLE as their order keys (fp_key32 / fp_key64,
 // the device's own functions), a DECIMAL's two words, everything else as given.
 void literal_words(const dr_predicate& p, int32_t k, int64_t* lo, int64_t* hi);

@@ -729,6 +729,57 @@ class State:
             lib.dr_agg_release(handle)
         return res
 
+    @staticmethod
+    def _bound(spec) -> Tuple[bytes, int]:
+        """(name, type_with_source) of a `(source, path, typ)` bound, named as agg_spec names a column."""
+        from .predicates import type_code, PredicateError
+        source, path, typ = spec
+        code = type_code(typ)
+        if code is None:
+            raise PredicateError("unsupported bound type %r" % (typ,))
+        name = "\x01".join([path] if isinstance(path, str) else list(path)).encode("utf-8")
+        return name, code | int(source) << N.DR_SRC_SHIFT
+
+    def probe_keys(self, lo, hi, keys, key_null=None, rows=None) -> Dict[str, "object"]:
+        """dr_state_probe_keys: which of the live export positions `rows` (None: every live file) can
+        hold any of `keys`, judged by the range [lo, hi] of each file. `lo` / `hi` are
+        `(source, path, typ)` as in agg_spec -- usually (N.DR_SRC_STATS_MIN, path, typ) and
+        (N.DR_SRC_STATS_MAX, path, typ), or one partition column twice. `keys` are int64 words encoded as
+        stats_column's values (float and double as their bits), in any order, repeats allowed;
+        `key_null` marks NULL keys (None: none is). Returns numpy arrays `selected` (positions, in
+        selection order), `hits` (distinct keys within the file's range, -1 where a statistic is
+        missing and the file cannot be skipped), `key_files` (per key, in the caller's order: the known
+        files whose range holds it) and the int `unknown`. The meaning of each field is in
+        include/deltareplay.h at dr_state_probe_keys."""
+        import numpy as np
+        lib = self.eng.lib
+        if not N.has_probe_keys(lib):
+            raise DeltaError(N.DR_E_UNSUPPORTED, "this libdeltareplay has no dr_state_probe_keys")
+        lo_name, lo_type = self._bound(lo)
+        hi_name, hi_type = self._bound(hi)
+        k = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        z = None if key_null is None else np.ascontiguousarray(key_null, dtype=np.uint8).reshape(-1)
+        if z is not None and z.size != k.size:
+            raise ValueError("key_null holds %d entries for %d keys" % (z.size, k.size))
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        rbuf = r if r is None or r.size else np.zeros(1, dtype=np.int64)  # an empty selection is no NULL pointer ("all")
+        p64, pu8 = C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+        handle = C.c_void_p()
+        out = N.dr_probe_result()
+        with self.eng.lock:
+            self.eng.check(lib.dr_state_probe_keys(
+                self.h, None if r is None else rbuf.ctypes.data_as(p64), 0 if r is None else r.size,
+                lo_name, lo_type, hi_name, hi_type, k.ctypes.data_as(p64) if k.size else None,
+                None if z is None or not z.size else z.ctypes.data_as(pu8), k.size, 0, C.byref(handle), C.byref(out)))
+        try:
+            def take(ptr, n):
+                return np.ctypeslib.as_array(ptr, shape=(max(n, 1),))[:n].copy()
+            res = {"selected": take(out.selected, out.nselected), "hits": take(out.hits, out.nselected),
+                   "key_files": take(out.key_files, out.nkeys), "unknown": int(out.unknown)}
+        finally:
+            lib.dr_probe_release(handle)
+        return res
+
     def partition_group_offsets(self, rows: Optional[Sequence[int]] = None):
         """dr_state_partition_groups as it comes: (order, group_off) -- the pair State.aggregate takes
         as `rows` and `groups`."""
@@ -928,6 +979,62 @@ class Snapshot:
             return self.state.export_rows_records(N.DR_LIVE, sel)  # the pruned rows alone
         files = self.all_files
         return list(files) if sel is None else [files[i] for i in sel]
+
+    _PROBE_TYPES = ("byte", "short", "integer", "long", "date", "timestamp", "float", "double")
+
+    def files_for_keys(self, column: str, keys: Sequence, filters: Sequence = (), data_skipping: bool = False):
+        """The files that can hold a row whose `column` equals any of `keys` -- the files a join or a
+        MERGE on that column touches (MergeIntoCommand.findTouchedFiles,
+        D/commands/MergeIntoCommand.scala:310, without the join) -- among those `filters` keep
+        (files_for_scan's rules, `data_skipping` included). `column` resolves as in filters: a partition
+        column (its value is the key: a semi-join; a NULL value joins nothing) or else a data column,
+        judged by its minValues / maxValues (a file without them is kept). `keys` are Python values of
+        the column's type as filter literals are (None: a NULL key, which joins nothing).
+        Returns (files, key_files): the AddFile records, and per key, in the caller's order, how many
+        of the files with known bounds can hold it (0: the key is in no file -- a pure insert -- unless
+        a file without statistics holds it).
+        No pruning, never a wrong skip: where the bounds cannot decide -- a column of a type
+        dr_state_probe_keys does not take, a timestamp data column (its statistics are truncated to
+        milliseconds), a NaN key against float / double statistics (they ignore NaN rows), a column
+        that does not resolve to one leaf -- every file of the filter selection comes back and
+        key_files is None. The probe runs on the GPU (dr_state_probe_keys)."""
+        import numpy as np
+        from .predicates import _lit, _resolve
+        from .skipping import data_schema, _name_segments
+        rows = self._scan_rows(filters, data_skipping)
+
+        def everything():
+            if rows is None:
+                return list(self.all_files), None
+            return self.state.export_rows_records(N.DR_LIVE, rows) if len(rows) else [], None
+        parts = (self.metadata or {}).get("partitionColumns") or []
+        part = _resolve(column, parts)
+        if part is not None:
+            typ = self.partition_schema()[part]
+            lo = hi = (N.DR_SRC_PARTITION, part, typ)
+        else:
+            segs = _name_segments(column)
+            want = tuple(s.lower() for s in segs or ())
+            leaves = [(p, t) for p, t in data_schema(self.metadata).items() if tuple(s.lower() for s in p) == want]
+            if len(leaves) != 1:
+                return everything()
+            path, typ = leaves[0]
+            lo, hi = (N.DR_SRC_STATS_MIN, path, typ), (N.DR_SRC_STATS_MAX, path, typ)
+        if typ not in self._PROBE_TYPES or (part is None and typ == "timestamp"):
+            return everything()
+        words = np.zeros(len(keys), dtype=np.int64)
+        nulls = np.zeros(len(keys), dtype=np.uint8)
+        for i, k in enumerate(keys):
+            w = None if k is None else _lit(typ, k)
+            if part is None and typ in ("float", "double") and isinstance(k, float) and k != k:
+                return everything()
+            if w is None or not -(1 << 63) <= w < (1 << 64):
+                nulls[i] = 1   # a NULL key, or an integer no column value can equal
+            else:
+                words[i] = w - (1 << 64) if w >= (1 << 63) else w  # a double's bits as the int64 word
+        res = self.state.probe_keys(lo, hi, words, nulls, rows)
+        sel = [int(r) for r in res["selected"]]
+        return (self.state.export_rows_records(N.DR_LIVE, sel) if sel else []), res["key_files"]
 
     def scan_sizes(self, filters: Sequence, data_skipping: bool = False) -> Dict[str, Dict[str, Optional[int]]]:
         """The three DataSize(bytesCompressed, rows) of DeltaScan (D/stats/DeltaScan.scala:29-52), which

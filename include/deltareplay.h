@@ -47,7 +47,10 @@ extern "C" {
  *      statistics column as a partition column of that name, so a host looks dr_state_stats_column up
  *      and sends no such column when the symbol is absent
  *      also within ABI 4: dr_state_aggregate / dr_agg_release (COUNT / MIN / MAX / SUM over the typed
- *      columns, size and modificationTime of a selection, per group); looked up like the others */
+ *      columns, size and modificationTime of a selection, per group); looked up like the others
+ *      also within ABI 4: dr_state_probe_keys / dr_probe_release (which files of a selection can hold
+ *      any key of a set, and how many files each key can lie in) and DR_OPT_PROBE_SEARCH; looked up
+ *      like the others */
 #define DR_ABI_VERSION 4
 
 /* Status codes. The JNI shim rethrows the reference's exception class with dr_last_error():
@@ -175,10 +178,15 @@ enum dr_option {
                                   config 4's 36 GB export stays pinned between snapshots); a released
                                   block evicts the largest cached ones to fit, one over the bound is
                                   unpinned at once */
-  DR_OPT_LOOKUP_KEY_BITS = 9   /* test hook: 64 (default); n in 1..64: the path index of
+  DR_OPT_LOOKUP_KEY_BITS = 9,  /* test hook: 64 (default); n in 1..64: the path index of
                                   dr_state_lookup_paths keeps only the low n bits of every replay key, in
                                   its build and its probes, so distinct paths share keys and probe runs
                                   grow long. Read when a state's index is built (its first lookup) */
+  DR_OPT_PROBE_SEARCH = 10     /* test and measurement hook, no tuning knob (both give the same result):
+                                  dr_state_probe_keys' search over the distinct keys. 0 (default) two levels,
+                                  a sampled splitter table in LDS and then one segment in global memory
+                                  (k_probe_files); 1 a plain binary search in global memory
+                                  (k_probe_files_plain, the variant DESIGN.md §4w times the first against) */
 };
 int dr_ctx_set_option(dr_ctx* ctx, int32_t option, int64_t value);
 int dr_ctx_get_option(dr_ctx* ctx, int32_t option, int64_t* value);
@@ -625,6 +633,62 @@ typedef struct dr_agg dr_agg;
 int dr_state_aggregate(dr_state* state, const int64_t* rows, int64_t nrows, const int64_t* group_off, int64_t ngroups,
                        const dr_agg_spec* aggs, int32_t naggs, dr_agg** handle, dr_agg_result* out);
 int dr_agg_release(dr_agg* handle);
+
+/* Key probe (an addition within ABI 4): which files of a selection can hold any key of a set -- the
+ * question a join or a MERGE asks of a snapshot. The reference answers it with a join of the source
+ * against the whole target (MergeIntoCommand.findTouchedFiles, D/commands/MergeIntoCommand.scala:310);
+ * with per-file statistics typed and cached on the device it is a range-against-set test per file, and
+ * the same pass counts, per key, the files it can lie in (none: a pure insert).
+ *
+ * Selection: dr_state_aggregate's rules. `rows` holds live export positions, in any order, repeats
+ * allowed; rows == NULL is every live file in export order (nrows is then ignored). A dr_filter result
+ * plugs in unchanged.
+ *
+ * Bounds: lo_* and hi_* are named and typed as a predicate column's (DR_SRC_PARTITION or DR_SRC_STATS_*
+ * in bits 24..27), built on first use and cached with dr_filter's columns. The usual pair is
+ * (DR_SRC_STATS_MIN c, DR_SRC_STATS_MAX c); the same partition column twice is a semi-join on that
+ * column. Both bounds have the same base type, one of BYTE, SHORT, INT, LONG, DATE, TIMESTAMP, FLOAT,
+ * DOUBLE; STRING, BINARY, DECIMAL and BOOLEAN are DR_E_UNSUPPORTED, as in dr_state_stats_column.
+ *
+ * Keys: keys[i] is encoded as dr_state_stats_column's values are (the integer kinds, DATE days and
+ * TIMESTAMP micros as int64; FLOAT as its bits, zero-extended -- the low 32 bits are read --; DOUBLE as
+ * its bits). key_null may be NULL (no key is NULL); a NULL key matches nothing. Keys need not be sorted or
+ * distinct: the library sorts and de-duplicates them on the device. Order and equality are dr_filter's:
+ * signed integers; FLOAT / DOUBLE as SQLOrderingUtil (-0.0 = 0.0, NaN = NaN, NaN above +Infinity). An
+ * integer key outside the column type's range is legal and matches nothing narrower than itself.
+ *
+ * Meaning. A selection position is selected iff some non-NULL key k has lo <= k AND k <= hi under that
+ * order; hits is then the number of distinct such keys (-0.0 and 0.0 are one key). It is also selected
+ * when a bound is NULL and that bound's source is a statistics source: the file cannot be skipped,
+ * hits = -1, and it is counted in `unknown` (this holds whatever the other bound is). Otherwise a NULL
+ * bound from DR_SRC_PARTITION is a NULL join key and is not selected. lo > hi selects nothing. `selected`
+ * keeps selection order (a repeated row appears as often as it is selected). key_files[i] counts, for the
+ * caller's key i, the known selection positions whose range holds it: unknown files are not counted, a
+ * repeated row counts twice, duplicated keys each get the same count, a NULL key gets 0. Nothing in the
+ * result depends on how the device cut the work or in which order its workgroups ran.
+ *
+ * *out's arrays live in one host block owned by *handle until dr_probe_release (a second release is
+ * DR_E_INVALID_ARG); the handle outlives the state and the context. nkeys == 0 is valid (only unknown
+ * files are selected), and so is an empty selection. DR_E_INVALID_ARG, before any device work and with
+ * the state left usable, naming the first offending index: flags != 0, nrows < 0 or above 2^32 - 1 (a
+ * key's files are counted in 32 bits on the device), nkeys < 0 or above 2^31 - 1, keys == NULL with nkeys > 0, a rows[i] outside the side, bounds of different base types, and
+ * what a predicate column of that source is refused for (its texts, "lo" / "hi" in the column's place).
+ * DR_E_UNSUPPORTED for the four types above and for a sharded state, as dr_state_lookup_paths. */
+typedef struct dr_probe_result {
+  int64_t nselected;
+  const int64_t* selected;   /* live export positions, in selection order */
+  const int64_t* hits;       /* [nselected] distinct non-NULL keys inside the file's range; -1 = unknown */
+  int64_t unknown;           /* how many selected files are unknown */
+  int64_t nkeys;
+  const int64_t* key_files;  /* [nkeys], caller's key order: selection positions whose range holds key i
+                                (unknown files not counted; a repeated row counts twice; NULL key: 0) */
+} dr_probe_result;
+typedef struct dr_probe dr_probe;
+int dr_state_probe_keys(dr_state* state, const int64_t* rows, int64_t nrows,
+                        const char* lo_name, int32_t lo_type, const char* hi_name, int32_t hi_type,
+                        const int64_t* keys, const uint8_t* key_null, int64_t nkeys, uint32_t flags,
+                        dr_probe** handle, dr_probe_result* out);
+int dr_probe_release(dr_probe* handle);
 void dr_free(void* p);
 
 /* ---- checkpoint writer --------------------------------------------------
