@@ -3517,6 +3517,19 @@ static void fix_fp_values(dr_ctx* ctx, dr_state::PvCol& col, const DBuf<uint64_t
   HIP_OK(hipStreamSynchronize(stream));
 }
 
+static PvColumn pv_column(const dr_state::PvCol& c) {
+  PvColumn p{};
+  p.type = c.type & ~int32_t(DR_SRC_MASK);
+  p.w32 = c.w32.p;
+  p.w64 = c.w64.p;
+  p.sptr = c.sptr.p;
+  p.slen = c.slen.p;
+  p.isnull = c.isnull.p;
+  p.s8 = c.s8.p;
+  p.w64hi = c.w64hi.p;
+  return p;
+}
+
 // One K5 cache column of n files, its buffers by its type; `pc`: the kernels' view of it (its type
 // without the source: the evaluators compare it with the bare dr_pred_type codes).
 static std::unique_ptr<dr_state::PvCol> new_pv_col(dr_ctx* ctx, uint64_t n, const std::string& name, int32_t type, PvColumn& pc) {
@@ -3524,32 +3537,82 @@ static std::unique_ptr<dr_state::PvCol> new_pv_col(dr_ctx* ctx, uint64_t n, cons
   col->name = name;
   col->type = type;
   col->isnull = DBuf<uint8_t>(ctx, n);
-  pc.type = type & ~int32_t(DR_SRC_MASK);
-  pc.isnull = col->isnull.p;
   const int base = type & 0xff;
   if (base == DR_T_STRING || base == DR_T_BINARY) {
     col->sptr = DBuf<uint64_t>(ctx, n);
     col->slen = DBuf<uint32_t>(ctx, n);
     col->s8 = DBuf<uint64_t>(ctx, n);
-    pc.sptr = col->sptr.p;
-    pc.slen = col->slen.p;
-    pc.s8 = col->s8.p;
   } else if (base == DR_T_LONG || base == DR_T_DOUBLE || base == DR_T_TIMESTAMP || base == DR_T_DECIMAL) {
     col->w64 = DBuf<int64_t>(ctx, n);
-    pc.w64 = col->w64.p;
     if (base == DR_T_DECIMAL) {
       col->w64hi = DBuf<int64_t>(ctx, n);
-      pc.w64hi = col->w64hi.p;
-      if (((type >> 8) & 0xff) <= 9) {
-        col->w32 = DBuf<uint32_t>(ctx, n);
-        pc.w32 = col->w32.p;
-      }
+      if (((type >> 8) & 0xff) <= 9) col->w32 = DBuf<uint32_t>(ctx, n);
     }
   } else {
     col->w32 = DBuf<uint32_t>(ctx, n);
-    pc.w32 = col->w32.p;
   }
+  pc = pv_column(*col);
   return col;
+}
+
+// What the two cache builds share. `a` arrives with its source filled in by the caller; this adds the
+// columns `want` of n files each, runs `launch` once -- or twice, when the first pass met values it
+// could not finish alone: escaped strings (unescaped into an arena, kept in st.pv_arenas) and
+// floating-point numbers off the device's exact path (listed for the host, fix_fp_values) -- hands
+// the kernel's error word to `check`, which fails on the bits its source raises, and publishes the
+// columns in st.pv_cols.
+template <typename Args, typename Check>
+static void extract_columns(dr_state& st, const std::vector<std::pair<std::string, int32_t>>& want, uint64_t n, Args& a,
+                            void (*launch)(const Args&, hipStream_t), Check&& check) {
+  dr_ctx* ctx = st.ctx;
+  hipStream_t stream = ctx->stream;
+  const size_t nc = want.size();
+  std::vector<uint64_t> name_off(nc + 1, 0);
+  std::string names;
+  for (size_t c = 0; c < nc; ++c) {
+    names += want[c].first;
+    name_off[c + 1] = names.size();
+  }
+  DBuf<uint64_t> d_name_off = upload(ctx, name_off.data(), name_off.size());
+  DBuf<uint8_t> d_names = upload(ctx, reinterpret_cast<const uint8_t*>(names.data()), names.size());
+  a.ncols = int32_t(nc);
+  a.col_name_off = d_name_off.p;
+  a.col_names = d_names.p;
+  std::vector<std::unique_ptr<dr_state::PvCol>> made;
+  for (size_t c = 0; c < nc; ++c) made.push_back(new_pv_col(ctx, n, want[c].first, want[c].second, a.cols[c]));
+  // counters: 0 arena fill, 1 arena need, 2.. per column: float / double values left to the host
+  DBuf<unsigned long long> ctr(ctx, 2 + nc);
+  DBuf<uint32_t> ferr(ctx, 1);
+  ctr.zero(stream);
+  ferr.zero(stream);
+  a.arena_fill = ctr.p;
+  a.arena_need = ctr.p + 1;
+  a.error = ferr.p;
+  for (size_t c = 0; c < nc; ++c) a.cols[c].nhard = ctr.p + 2 + c;
+  launch(a, stream);
+  const std::vector<unsigned long long> cnt = d2h(ctr.p, 2 + nc, stream);
+  std::vector<DBuf<uint64_t>> hard(nc);
+  bool rerun = cnt[1] != 0;
+  for (size_t c = 0; c < nc; ++c)
+    if (cnt[2 + c]) {
+      hard[c] = DBuf<uint64_t>(ctx, 3 * cnt[2 + c]);
+      a.cols[c].hard = hard[c].p;
+      rerun = true;
+    }
+  if (rerun) {
+    if (cnt[1]) {
+      auto arena = std::make_shared<DBuf<uint8_t>>(ctx, cnt[1] + 64);
+      a.arena = arena->p;
+      a.arena_cap = cnt[1] + 64;
+      st.pv_arenas.push_back(arena);
+    }
+    HIP_OK(hipMemsetAsync(ctr.p, 0, 8 * (2 + nc), stream));
+    launch(a, stream);
+  }
+  check(d2h_one(ferr.p, stream));
+  for (size_t c = 0; c < nc; ++c)
+    if (cnt[2 + c]) fix_fp_values(ctx, *made[c], hard[c], cnt[2 + c]);
+  for (auto& c : made) st.pv_cols.push_back(std::move(c));
 }
 
 // Builds the K5 cache columns `want` (name, type) of st's live AddFiles in one k_pv_extract pass.
@@ -3621,65 +3684,16 @@ static void build_pv_columns(dr_state& st, const std::vector<std::pair<std::stri
       a.val_def = vdef.p; a.val_ptr = vptr.p; a.val_len = vlen.p; a.val_max_def = P.max_def[1];
     }
   }
-  std::vector<uint64_t> name_off(want.size() + 1, 0);
-  std::string names;
-  for (size_t c = 0; c < want.size(); ++c) {
-    names += want[c].first;
-    name_off[c + 1] = names.size();
-  }
-  DBuf<uint64_t> d_name_off = upload(ctx, name_off.data(), name_off.size());
-  DBuf<uint8_t> d_names = upload(ctx, reinterpret_cast<const uint8_t*>(names.data()), names.size());
-  a.ncols = int32_t(want.size());
-  a.col_name_off = d_name_off.p;
-  a.col_names = d_names.p;
-  std::vector<std::unique_ptr<dr_state::PvCol>> made;
-  for (size_t c = 0; c < want.size(); ++c) made.push_back(new_pv_col(ctx, n, want[c].first, want[c].second, a.cols[c]));
-  // counters: 0 arena fill, 1 arena need, 2.. per column: float / double values left to the host
-  const size_t nc = want.size();
-  DBuf<unsigned long long> ctr(ctx, 2 + nc);
-  DBuf<uint32_t> ferr(ctx, 1);
-  ctr.zero(stream);
-  ferr.zero(stream);
-  a.arena_fill = ctr.p;
-  a.arena_need = ctr.p + 1;
-  a.error = ferr.p;
-  for (size_t c = 0; c < nc; ++c) a.cols[c].nhard = ctr.p + 2 + c;
-  launch_pv_extract(a, stream);
-  const std::vector<unsigned long long> cnt = d2h(ctr.p, 2 + nc, stream);
-  std::vector<DBuf<uint64_t>> hard(nc);
-  bool rerun = cnt[1] != 0;
-  for (size_t c = 0; c < nc; ++c)
-    if (cnt[2 + c]) {
-      hard[c] = DBuf<uint64_t>(ctx, 3 * cnt[2 + c]);
-      a.cols[c].hard = hard[c].p;
-      rerun = true;
-    }
-  if (rerun) {
-    // some partition values carry JSON escapes (unescaped into an arena) or are floating-point
-    // numbers off the device's exact path (listed for the host): rerun with those buffers
-    if (cnt[1]) {
-      auto arena = std::make_shared<DBuf<uint8_t>>(ctx, cnt[1] + 64);
-      a.arena = arena->p;
-      a.arena_cap = cnt[1] + 64;
-      st.pv_arenas.push_back(arena);
-    }
-    HIP_OK(hipMemsetAsync(ctr.p, 0, 8 * (2 + nc), stream));
-    launch_pv_extract(a, stream);
-  }
-  const uint32_t e = d2h_one(ferr.p, stream);
-  if (e & 1u) fail(DR_E_PARSE, "malformed add.partitionValues in a live AddFile's JSON line");
-  if (e & 2u) fail(DR_E_INTERNAL, "partition value arena overflow");
-  for (size_t c = 0; c < nc; ++c)
-    if (cnt[2 + c]) fix_fp_values(ctx, *made[c], hard[c], cnt[2 + c]);
-  for (auto& c : made) st.pv_cols.push_back(std::move(c));
+  extract_columns(st, want, n, a, launch_pv_extract, [](uint32_t e) {
+    if (e & 1u) fail(DR_E_PARSE, "malformed add.partitionValues in a live AddFile's JSON line");
+    if (e & 2u) fail(DR_E_INTERNAL, "partition value arena overflow");
+  });
 }
 
 // Builds the statistics cache columns `want` (path, type with its DR_SRC_STATS_* source) of st's live
 // AddFiles in one k_stats_extract pass over the live side's resident export columns (materialised on
 // first use: one source for JSON lines, checkpoint rows and applied states, the line's escaping gone).
 static void build_stats_columns(dr_state& st, const std::vector<std::pair<std::string, int32_t>>& want) {
-  dr_ctx* ctx = st.ctx;
-  hipStream_t stream = ctx->stream;
   const DevExport& X = materialize(st, DR_LIVE);
   const uint64_t n = X.n;
   if (n != st.n_live) fail(DR_E_INTERNAL, "statistics columns: the materialised live side disagrees with the state");
@@ -3688,69 +3702,38 @@ static void build_stats_columns(dr_state& st, const std::vector<std::pair<std::s
   a.stats_null = X.stats_null.p;
   a.stats_off = X.off[EXC_STATS].p;
   a.stats_bytes = X.stats_bytes.p;
-  const size_t nc = want.size();
-  std::vector<uint64_t> name_off(nc + 1, 0);
-  std::string names;
-  for (size_t c = 0; c < nc; ++c) {
-    names += want[c].first;
-    name_off[c + 1] = names.size();
-  }
-  DBuf<uint64_t> d_name_off = upload(ctx, name_off.data(), name_off.size());
-  DBuf<uint8_t> d_names = upload(ctx, reinterpret_cast<const uint8_t*>(names.data()), names.size());
-  a.ncols = int32_t(nc);
-  a.col_name_off = d_name_off.p;
-  a.col_names = d_names.p;
-  std::vector<std::unique_ptr<dr_state::PvCol>> made;
-  for (size_t c = 0; c < nc; ++c) {
-    a.src[c] = (want[c].second >> DR_SRC_SHIFT) & 0xf;
-    made.push_back(new_pv_col(ctx, n, want[c].first, want[c].second, a.cols[c]));
-  }
-  // counters: 0 arena fill, 1 arena need, 2.. per column: float / double values left to the host
-  DBuf<unsigned long long> ctr(ctx, 2 + nc);
-  DBuf<uint32_t> ferr(ctx, 1);
-  ctr.zero(stream);
-  ferr.zero(stream);
-  a.arena_fill = ctr.p;
-  a.arena_need = ctr.p + 1;
-  a.error = ferr.p;
-  for (size_t c = 0; c < nc; ++c) a.cols[c].nhard = ctr.p + 2 + c;
-  launch_stats_extract(a, stream);
-  const std::vector<unsigned long long> cnt = d2h(ctr.p, 2 + nc, stream);
-  std::vector<DBuf<uint64_t>> hard(nc);
-  bool rerun = cnt[1] != 0;
-  for (size_t c = 0; c < nc; ++c)
-    if (cnt[2 + c]) {
-      hard[c] = DBuf<uint64_t>(ctx, 3 * cnt[2 + c]);
-      a.cols[c].hard = hard[c].p;
-      rerun = true;
-    }
-  if (rerun) {  // escaped string values (into an arena) or numbers for the host's strtod: with those buffers
-    if (cnt[1]) {
-      auto arena = std::make_shared<DBuf<uint8_t>>(ctx, cnt[1] + 64);
-      a.arena = arena->p;
-      a.arena_cap = cnt[1] + 64;
-      st.pv_arenas.push_back(arena);
-    }
-    HIP_OK(hipMemsetAsync(ctr.p, 0, 8 * (2 + nc), stream));
-    launch_stats_extract(a, stream);
-  }
-  if (d2h_one(ferr.p, stream) & 2u) fail(DR_E_INTERNAL, "statistics value arena overflow");
-  for (size_t c = 0; c < nc; ++c)
-    if (cnt[2 + c]) fix_fp_values(ctx, *made[c], hard[c], cnt[2 + c]);
-  for (auto& c : made) st.pv_cols.push_back(std::move(c));
+  for (size_t c = 0; c < want.size(); ++c) a.src[c] = (want[c].second >> DR_SRC_SHIFT) & 0xf;
+  extract_columns(st, want, n, a, launch_stats_extract, [](uint32_t e) {
+    if (e & 2u) fail(DR_E_INTERNAL, "statistics value arena overflow");
+  });
 }
 
-static PvColumn pv_column(const dr_state::PvCol& c) {
-  PvColumn p{};
-  p.type = c.type & ~int32_t(DR_SRC_MASK);
-  p.w32 = c.w32.p;
-  p.w64 = c.w64.p;
-  p.sptr = c.sptr.p;
-  p.slen = c.slen.p;
-  p.isnull = c.isnull.p;
-  p.s8 = c.s8.p;
-  p.w64hi = c.w64hi.p;
-  return p;
+// The only way to a cache column: one pointer per key (name, type with its source bits), in key order,
+// the same pointer for a repeated key. The keys not cached yet are built first -- each once, the
+// partition values in one k_pv_extract pass, then the statistics in one k_stats_extract pass -- and
+// stay with the state. A state without live files has nothing to build: every pointer is null.
+static std::vector<dr_state::PvCol*> ensure_columns(dr_state& st, const std::vector<std::pair<std::string, int32_t>>& keys) {
+  std::vector<dr_state::PvCol*> cols(keys.size(), nullptr);
+  if (!st.n_live) return cols;
+  auto lookup = [&] {
+    size_t found = 0;
+    for (size_t k = 0; k < keys.size(); ++k) {
+      for (auto& c : st.pv_cols)
+        if (c->name == keys[k].first && c->type == keys[k].second) cols[k] = c.get();
+      found += cols[k] != nullptr;
+    }
+    return found == keys.size();
+  };
+  if (lookup()) return cols;
+  std::vector<std::pair<std::string, int32_t>> missing[2];  // by source: partition values, statistics
+  for (size_t k = 0; k < keys.size(); ++k) {
+    auto& into = missing[(keys[k].second & DR_SRC_MASK) != 0];
+    if (!cols[k] && std::find(into.begin(), into.end(), keys[k]) == into.end()) into.push_back(keys[k]);
+  }
+  if (!missing[0].empty()) build_pv_columns(st, missing[0]);
+  if (!missing[1].empty()) build_stats_columns(st, missing[1]);
+  if (!lookup()) fail(DR_E_INTERNAL, "a cache column was not built");
+  return cols;
 }
 
 // Dictionary-encodes a typed partition column (k_dict_*): abandoned (dict = 0) past DICT_MAX - 1
@@ -3821,37 +3804,15 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& given
   hipStream_t stream = ctx->stream;
   if (st.sources.empty()) fail(DR_E_INVALID_ARG, "state has no staged segment");
   // the predicate's columns in the K5 cache (built for the ones not there yet)
-  auto find = [&](const std::string& name, int32_t type) -> dr_state::PvCol* {
-    for (auto& c : st.pv_cols)
-      if (c->name == name && c->type == type) return c.get();
-    return nullptr;
-  };
-  std::vector<std::pair<std::string, int32_t>> want;
-  for (int32_t c = 0; c < pred.ncols; ++c) {
-    std::pair<std::string, int32_t> k{pred.col_names[c], pred.col_types[c]};
-    if (!find(k.first, k.second) && std::find(want.begin(), want.end(), k) == want.end()) want.push_back(k);
-  }
-  // by source: partition values from the records' own bytes, statistics from the resident stats column
-  std::vector<std::pair<std::string, int32_t>> want_stats;
-  for (auto it = want.begin(); it != want.end();)
-    if (it->second & DR_SRC_MASK) {
-      want_stats.push_back(*it);
-      it = want.erase(it);
-    } else {
-      ++it;
-    }
-  if (!want.empty() && st.n_live) build_pv_columns(st, want);
-  if (!want_stats.empty() && st.n_live) build_stats_columns(st, want_stats);
+  std::vector<std::pair<std::string, int32_t>> keys;
+  for (int32_t c = 0; c < pred.ncols; ++c) keys.push_back({pred.col_names[c], pred.col_types[c]});
+  const std::vector<dr_state::PvCol*> pcols = ensure_columns(st, keys);
   FilterTypedArgs fa{};
   fa.n_live = st.n_live;
   fa.ncols = pred.ncols;
   for (int32_t c = 0; c < pred.ncols; ++c) {
-    dr_state::PvCol* col = find(pred.col_names[c], pred.col_types[c]);
-    if (!col) {  // no live files: nothing was built
-      fa.cols[c].type = pred.col_types[c] & ~int32_t(DR_SRC_MASK);
-      continue;
-    }
-    fa.cols[c] = pv_column(*col);
+    if (pcols[c]) fa.cols[c] = pv_column(*pcols[c]);
+    else fa.cols[c].type = pred.col_types[c] & ~int32_t(DR_SRC_MASK);  // no live files: nothing was built
   }
   LeafPlan lp;
   const bool force_generic = ctx->opt.filter_eval == 2;  // DR_OPT_FILTER_EVAL: k_filter_typed
@@ -3893,7 +3854,7 @@ static std::vector<int64_t> filter_state(dr_state& st, const dr_predicate& given
     la.wg_count = wg_count.p;
     // the dictionary path when every column the leaves read has a dictionary and the leaf tables fit
     std::vector<dr_state::PvCol*> ucols;
-    for (int32_t u = 0; u < la.nucol; ++u) ucols.push_back(find(pred.col_names[la.ucol[u]], pred.col_types[la.ucol[u]]));
+    for (int32_t u = 0; u < la.nucol; ++u) ucols.push_back(pcols[size_t(la.ucol[u])]);
     bool use_dict = la.nucol > 0 && st.n_live && ctx->opt.filter_eval == 0;  // DR_OPT_FILTER_EVAL
     for (dr_state::PvCol* c : ucols) {
       if (!use_dict || !c) { use_dict = false; break; }
@@ -4347,15 +4308,7 @@ static void write_checkpoint_part(dr_state& st, int32_t part, int32_t parts, uin
       }
     }
   }
-  if (!parsed.empty()) {
-    std::vector<std::pair<std::string, int32_t>> want;
-    for (auto& pc : parsed) {
-      bool have = false;
-      for (auto& c : st.pv_cols) have |= c->name == pc.first && c->type == pc.second;
-      if (!have) want.push_back(pc);
-    }
-    if (!want.empty() && st.n_live) build_pv_columns(st, want);
-  }
+  const std::vector<dr_state::PvCol*> parsed_cols = ensure_columns(st, parsed);  // null without live files
   // only the records of this part: adds [a0, a1), removes [b0, b1) (side-relative)
   const uint64_t a0 = std::min(NA, p0 > H ? p0 - H : 0), a1 = std::min(NA, p1 > H ? p1 - H : 0);
   const uint64_t b0 = std::min(NR, p0 > H + NA ? p0 - H - NA : 0), b1 = std::min(NR, p1 > H + NA ? p1 - H - NA : 0);
@@ -4456,9 +4409,9 @@ static void write_checkpoint_part(dr_state& st, int32_t part, int32_t parts, uin
     if (!parsed.empty()) {
       group("partitionValues_parsed", PR_OPTIONAL, int(parsed.size()));
       at.push_back("partitionValues_parsed");
-      for (auto& pc : parsed) {
-        const dr_state::PvCol* col = nullptr;
-        for (auto& c : st.pv_cols) if (c->name == pc.first && c->type == pc.second) col = c.get();
+      for (size_t k = 0; k < parsed.size(); ++k) {
+        const auto& pc = parsed[k];
+        const dr_state::PvCol* col = parsed_cols[k];
         EncLeaf f{};
         f.def_null = 2;
         f.def_present = 3;
@@ -4923,22 +4876,16 @@ static void partition_groups(dr_state& st, const int64_t* rows, int64_t nrows, s
     off.push_back(int64_t(n));
     return;
   }
-  std::vector<std::pair<std::string, int32_t>> want;
-  for (const std::string& c : cols) {
-    bool have = false;
-    for (auto& pc : st.pv_cols) have |= pc->name == c && pc->type == DR_T_STRING;
-    if (!have) want.push_back({c, DR_T_STRING});
-  }
-  if (!want.empty()) build_pv_columns(st, want);
+  std::vector<std::pair<std::string, int32_t>> col_keys;
+  for (const std::string& c : cols) col_keys.push_back({c, DR_T_STRING});
+  const std::vector<dr_state::PvCol*> pcols = ensure_columns(st, col_keys);  // n > 0: the state has live files
   GroupCols g{};
   g.ncols = int32_t(cols.size());
-  for (size_t c = 0; c < cols.size(); ++c)
-    for (auto& pc : st.pv_cols)
-      if (pc->name == cols[c] && pc->type == DR_T_STRING) {
-        g.sptr[c] = pc->sptr.p;
-        g.slen[c] = pc->slen.p;
-        g.isnull[c] = pc->isnull.p;
-      }
+  for (size_t c = 0; c < cols.size(); ++c) {
+    g.sptr[c] = pcols[c]->sptr.p;
+    g.slen[c] = pcols[c]->slen.p;
+    g.isnull[c] = pcols[c]->isnull.p;
+  }
   DBuf<uint32_t> keys(ctx, n);
   if (rows) {
     std::vector<uint32_t> r(rows, rows + n);
@@ -5613,6 +5560,47 @@ int guard(dr_ctx* ctx, F&& f) {
     return DR_E_INTERNAL;
   }
 }
+
+// guard for a call that begins a timed call (dr_ctx::begin_call): a failure leaves neither the launch
+// hook installed nor event marks queued for the next call to report.
+template <typename F>
+int guard_timed(dr_ctx* ctx, F&& f) {
+  const int rc = guard(ctx, std::forward<F>(f));
+  if (rc != DR_OK) {
+    std::lock_guard<std::recursive_mutex> g(ctx->api_mu);
+    ctx->drop_timings();
+  }
+  return rc;
+}
+
+// A malloc'ed copy of v for the caller to free (never null: an empty v gets room for one element).
+template <typename T>
+T* malloc_copy(const std::vector<T>& v) {
+  T* out = static_cast<T*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(T)));
+  if (!out) throw std::bad_alloc();
+  if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(T));
+  return out;
+}
+
+// The live handles of one kind of host result (dr_agg, dr_probe): plain host memory with no tie to
+// its context or state, registered so that a second release is refused instead of freeing twice.
+template <typename T>
+struct Handles {
+  std::mutex mu;
+  std::unordered_set<T*> live;
+  T* adopt(std::unique_ptr<T> h) {
+    std::lock_guard<std::mutex> g(mu);
+    live.insert(h.get());
+    return h.release();
+  }
+  int release(T* h) {
+    if (!h) return DR_OK;
+    std::lock_guard<std::mutex> g(mu);
+    if (!live.erase(h)) return DR_E_INVALID_ARG;  // not a live handle (released twice)
+    delete h;
+    return DR_OK;
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -5882,14 +5870,12 @@ int dr_staged_plan(const dr_staged* staged, uint64_t* out, int32_t cap, int32_t*
 int dr_replay_staged(dr_ctx* ctx, const dr_staged* staged, int64_t cutoff, uint32_t flags, dr_state** out) {
   if (!ctx || !staged || !out) return DR_E_INVALID_ARG;
   *out = nullptr;
-  int rc = guard(ctx, [&] {
+  return guard_timed(ctx, [&] {
     HIP_OK(hipSetDevice(ctx->device));
     ctx->begin_call();
     *out = replay(ctx, staged->d, cutoff, flags);
     ctx->collect_timings();
   });
-  if (rc != DR_OK) ctx->drop_timings();
-  return rc;
 }
 
 int dr_replay(dr_ctx* ctx, const dr_file* files, int32_t nfiles, int64_t cutoff, uint32_t flags, dr_state** out) {
@@ -5913,7 +5899,7 @@ int dr_state_apply(dr_ctx* ctx, dr_state* base, const dr_staged* tail, int64_t m
                    uint32_t flags, dr_state** out) {
   if (!ctx || !base || !tail || !out) return DR_E_INVALID_ARG;
   *out = nullptr;
-  int rc = guard(ctx, [&] {
+  return guard_timed(ctx, [&] {
     HIP_OK(hipSetDevice(ctx->device));
     ctx->begin_call();
     ctx->mark("start");
@@ -5921,8 +5907,6 @@ int dr_state_apply(dr_ctx* ctx, dr_state* base, const dr_staged* tail, int64_t m
     ctx->mark("end");
     ctx->collect_timings();
   });
-  if (rc != DR_OK) ctx->drop_timings();
-  return rc;
 }
 
 int dr_state_counts(dr_state* state, dr_counts* out) {
@@ -6029,8 +6013,6 @@ int dr_state_export(dr_state* state, int32_t which, dr_export* out) {
     fill_export(out, e, e.n);
   });
 }
-
-static int64_t* malloc_copy(const std::vector<int64_t>& v);
 
 // ---- row-range export (ABI 3) ------------------------------------------------------------------
 // A host copy of rows [lo, hi) of one side's resident export columns, every offset array rebased to
@@ -6502,7 +6484,7 @@ int dr_state_lookup_paths(dr_state* state, const uint8_t* path_bytes, const int6
                           uint32_t flags, uint8_t* hit, int64_t* row) {
   if (!state) return DR_E_INVALID_ARG;
   dr_ctx* ctx = state->ctx;
-  const int rc = guard(ctx, [&] {
+  return guard_timed(ctx, [&] {
     // the arguments first: nothing is built, staged or read through them before they hold
     lookup_check(path_bytes, path_off, npaths, flags, hit, row);
     if (state->sharded)
@@ -6514,11 +6496,6 @@ int dr_state_lookup_paths(dr_state* state, const uint8_t* path_bytes, const int6
     lookup_paths(*state, path_bytes, path_off, uint64_t(npaths), hit, row);
     ctx->collect_timings();
   });
-  if (rc != DR_OK) {
-    std::lock_guard<std::recursive_mutex> g(ctx->api_mu);
-    ctx->drop_timings();
-  }
-  return rc;
 }
 
 int dr_range_release(dr_range* range) {
@@ -6572,13 +6549,10 @@ int dr_filter(dr_state* state, const dr_predicate* pred, int64_t** selected, int
   if (!state || !pred || !selected || !nselected) return DR_E_INVALID_ARG;
   *selected = nullptr;
   *nselected = 0;
-  return guard(state->ctx, [&] {
+  return guard_timed(state->ctx, [&] {
     HIP_OK(hipSetDevice(state->ctx->device));
     std::vector<int64_t> v = filter_state(*state, *pred);
-    int64_t* out = static_cast<int64_t*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(int64_t)));
-    if (!out) throw std::bad_alloc();
-    if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(int64_t));
-    *selected = out;
+    *selected = malloc_copy(v);
     *nselected = int64_t(v.size());
   });
 }
@@ -6601,13 +6575,7 @@ static void stats_column(dr_state& st, const char* name, int32_t type, std::vect
   values.clear();
   nulls.clear();
   if (!st.n_live) return;
-  auto find = [&]() -> dr_state::PvCol* {
-    for (auto& c : st.pv_cols)
-      if (c->name == name && c->type == type) return c.get();
-    return nullptr;
-  };
-  if (!find()) build_stats_columns(st, {{std::string(name), type}});
-  const dr_state::PvCol& col = *find();
+  const dr_state::PvCol& col = *ensure_columns(st, {{std::string(name), type}})[0];
   nulls = d2h(col.isnull.p, st.n_live, stream);
   if (col.w64.p) {
     values = d2h(col.w64.p, st.n_live, stream);
@@ -6627,35 +6595,25 @@ int dr_state_stats_column(dr_state* state, const char* name, int32_t type_with_s
   *values = nullptr;
   *isnull = nullptr;
   *n = 0;
-  return guard(state->ctx, [&] {
+  return guard_timed(state->ctx, [&] {
     HIP_OK(hipSetDevice(state->ctx->device));
     std::vector<int64_t> v;
     std::vector<uint8_t> z;
     stats_column(*state, name, type_with_source, v, z);
-    int64_t* out = static_cast<int64_t*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(int64_t)));
-    uint8_t* outz = static_cast<uint8_t*>(malloc(std::max<size_t>(z.size(), 1)));
-    if (!out || !outz) {
-      free(out);
-      free(outz);
-      throw std::bad_alloc();
-    }
-    if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(int64_t));
-    if (!z.empty()) memcpy(outz, z.data(), z.size());
-    *values = out;
-    *isnull = outz;
+    std::unique_ptr<int64_t, decltype(&free)> out(malloc_copy(v), &free);  // freed if the second copy fails
+    *isnull = malloc_copy(z);
+    *values = out.release();
     *n = int64_t(v.size());
   });
 }
 
 // dr_state_aggregate's result: one host block that holds every array of the dr_agg_result. It is plain
-// host memory with no tie to its context or state, so it outlives both; live handles are registered so
-// that a second release is refused instead of freeing twice.
+// host memory with no tie to its context or state, so it outlives both (Handles).
 struct dr_agg {
   std::vector<int64_t> words;   // group_rows, nonnull, value_lo, value_hi, arg_row, str_off
   std::vector<uint8_t> bytes;   // str_bytes
 };
-static std::mutex g_aggs_mu;
-static std::unordered_set<dr_agg*> g_aggs;
+static Handles<dr_agg> g_agg_handles;
 
 // The reduction of `aggs` over the selection (k_agg.hip). The arguments have passed check_agg_specs and
 // check_agg_selection. rows and group_off are uploaded whole (8 B a row: 80 MB for 10M selected files,
@@ -6678,25 +6636,19 @@ static void aggregate_state(dr_state& st, const int64_t* rows, uint64_t n, const
   for (uint64_t g = 0; g < ngroups; ++g) group_rows[g] = group_off ? group_off[g + 1] - group_off[g] : int64_t(n);
   std::fill(arg_row, arg_row + cells, int64_t(-1));
   if (n && cells) {
-    auto find = [&](const std::string& name, int32_t type) -> dr_state::PvCol* {
-      for (auto& c : st.pv_cols)
-        if (c->name == name && c->type == type) return c.get();
-      return nullptr;
-    };
-    // the specs' columns in the K5 cache (built for the ones not there yet, by source as dr_filter does)
-    std::vector<std::pair<std::string, int32_t>> want, want_stats;
+    // the specs' columns in the K5 cache: pcols[at[a]] is spec a's (n > 0: the state has live files)
+    std::vector<std::pair<std::string, int32_t>> keys;
+    std::vector<size_t> at(size_t(naggs), 0);
     bool builtin = false;
     for (int32_t a = 0; a < naggs; ++a) {
       if (aggs[a].input != DR_AGG_IN_COLUMN) {
         builtin = true;
         continue;
       }
-      std::pair<std::string, int32_t> k{aggs[a].name, aggs[a].type_with_source};
-      auto& into = (k.second & DR_SRC_MASK) ? want_stats : want;
-      if (!find(k.first, k.second) && std::find(into.begin(), into.end(), k) == into.end()) into.push_back(k);
+      at[size_t(a)] = keys.size();
+      keys.push_back({aggs[a].name, aggs[a].type_with_source});
     }
-    if (!want.empty()) build_pv_columns(st, want);
-    if (!want_stats.empty()) build_stats_columns(st, want_stats);
+    const std::vector<dr_state::PvCol*> pcols = ensure_columns(st, keys);
     const DevExport* X = builtin ? &materialize(st, DR_LIVE) : nullptr;
     if (X && X->n != st.n_live) fail(DR_E_INTERNAL, "aggregate: the materialised live side disagrees with the state");
     AggArgs A{};
@@ -6711,8 +6663,7 @@ static void aggregate_state(dr_state& st, const int64_t* rows, uint64_t n, const
         s.kind = AGK_I64;
         s.v = aggs[a].input == DR_AGG_IN_SIZE ? X->size.p : X->mtime.p;
       } else {
-        const dr_state::PvCol* col = find(aggs[a].name, aggs[a].type_with_source);
-        if (!col) fail(DR_E_INTERNAL, "aggregate: a cache column was not built");
+        const dr_state::PvCol* col = pcols[at[size_t(a)]];
         const int base = col->type & 0xff;
         s.isnull = col->isnull.p;
         if (base == DR_T_STRING || base == DR_T_BINARY) {
@@ -6790,7 +6741,7 @@ int dr_state_aggregate(dr_state* state, const int64_t* rows, int64_t nrows, cons
   *handle = nullptr;
   memset(out, 0, sizeof(*out));
   dr_ctx* ctx = state->ctx;
-  const int rc = guard(ctx, [&] {
+  const int rc = guard_timed(ctx, [&] {
     // the arguments first: nothing is built, staged or read through them before they hold
     check_agg_specs(aggs, naggs);
     if (state->sharded)
@@ -6804,33 +6755,20 @@ int dr_state_aggregate(dr_state* state, const int64_t* rows, int64_t nrows, cons
     auto R = std::make_unique<dr_agg>();
     aggregate_state(*state, rows, rows ? uint64_t(nrows) : state->n_live, group_off, group_off ? uint64_t(ngroups) : 1, aggs,
                     naggs, *R, out);
-    std::lock_guard<std::mutex> g(g_aggs_mu);
-    g_aggs.insert(R.get());
-    *handle = R.release();
+    *handle = g_agg_handles.adopt(std::move(R));
   });
-  if (rc != DR_OK) {
-    memset(out, 0, sizeof(*out));
-    std::lock_guard<std::recursive_mutex> g(ctx->api_mu);
-    ctx->drop_timings();
-  }
+  if (rc != DR_OK) memset(out, 0, sizeof(*out));
   return rc;
 }
 
-int dr_agg_release(dr_agg* handle) {
-  if (!handle) return DR_OK;
-  std::lock_guard<std::mutex> g(g_aggs_mu);
-  if (!g_aggs.erase(handle)) return DR_E_INVALID_ARG;  // not a live handle (released twice)
-  delete handle;
-  return DR_OK;
-}
+int dr_agg_release(dr_agg* handle) { return g_agg_handles.release(handle); }
 
 // dr_state_probe_keys' result: one host block, registered like a dr_agg so that it outlives its state
 // and context and a second release is refused.
 struct dr_probe {
   std::vector<int64_t> words;   // selected, hits, key_files
 };
-static std::mutex g_probes_mu;
-static std::unordered_set<dr_probe*> g_probes;
+static Handles<dr_probe> g_probe_handles;
 
 // The probe of the selection's [lo, hi] ranges against the keys (k_probe.hip). The arguments have passed
 // check_probe_args and check_probe_rows. Up go 8 B a key (9 with a null mask) and 8 B a given row; down
@@ -6844,22 +6782,9 @@ static void probe_state(dr_state& st, const int64_t* rows, uint64_t n, const cha
   hipStream_t stream = ctx->stream;
   std::vector<int64_t> sel, sel_hits, key_files(nkeys, 0);
   if (n) {
-    auto find = [&](const std::string& name, int32_t type) -> dr_state::PvCol* {
-      for (auto& c : st.pv_cols)
-        if (c->name == name && c->type == type) return c.get();
-      return nullptr;
-    };
-    // the two bounds in the K5 cache (built when not there yet, by source as dr_filter does)
-    std::vector<std::pair<std::string, int32_t>> want, want_stats;
-    for (const auto& k : {std::pair<std::string, int32_t>{lo_name, lo_type}, std::pair<std::string, int32_t>{hi_name, hi_type}}) {
-      auto& into = (k.second & DR_SRC_MASK) ? want_stats : want;
-      if (!find(k.first, k.second) && std::find(into.begin(), into.end(), k) == into.end()) into.push_back(k);
-    }
-    if (!want.empty()) build_pv_columns(st, want);
-    if (!want_stats.empty()) build_stats_columns(st, want_stats);
-    const dr_state::PvCol* lo = find(lo_name, lo_type);
-    const dr_state::PvCol* hi = find(hi_name, hi_type);
-    if (!lo || !hi) fail(DR_E_INTERNAL, "probe_keys: a cache column was not built");
+    // the two bounds in the K5 cache (n > 0: the state has live files)
+    const std::vector<dr_state::PvCol*> bounds = ensure_columns(st, {{lo_name, lo_type}, {hi_name, hi_type}});
+    const dr_state::PvCol *lo = bounds[0], *hi = bounds[1];
     const int32_t base = lo_type & 0xff;
     ProbeArgs A{};
     A.n = n;
@@ -6963,7 +6888,7 @@ int dr_state_probe_keys(dr_state* state, const int64_t* rows, int64_t nrows, con
   *handle = nullptr;
   memset(out, 0, sizeof(*out));
   dr_ctx* ctx = state->ctx;
-  const int rc = guard(ctx, [&] {
+  const int rc = guard_timed(ctx, [&] {
     // the arguments first: nothing is built, staged or read through them before they hold
     check_probe_args(rows != nullptr, nrows, lo_name, lo_type, hi_name, hi_type, keys, nkeys, flags);
     if (state->sharded)
@@ -6977,38 +6902,19 @@ int dr_state_probe_keys(dr_state* state, const int64_t* rows, int64_t nrows, con
     auto R = std::make_unique<dr_probe>();
     probe_state(*state, rows, rows ? uint64_t(nrows) : state->n_live, lo_name, lo_type, hi_name, hi_type, keys, key_null,
                 uint64_t(nkeys), *R, out);
-    std::lock_guard<std::mutex> g(g_probes_mu);
-    g_probes.insert(R.get());
-    *handle = R.release();
+    *handle = g_probe_handles.adopt(std::move(R));
   });
-  if (rc != DR_OK) {
-    memset(out, 0, sizeof(*out));
-    std::lock_guard<std::recursive_mutex> g(ctx->api_mu);
-    ctx->drop_timings();
-  }
+  if (rc != DR_OK) memset(out, 0, sizeof(*out));
   return rc;
 }
 
-int dr_probe_release(dr_probe* handle) {
-  if (!handle) return DR_OK;
-  std::lock_guard<std::mutex> g(g_probes_mu);
-  if (!g_probes.erase(handle)) return DR_E_INVALID_ARG;  // not a live handle (released twice)
-  delete handle;
-  return DR_OK;
-}
-
-static int64_t* malloc_copy(const std::vector<int64_t>& v) {
-  int64_t* out = static_cast<int64_t*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(int64_t)));
-  if (!out) throw std::bad_alloc();
-  if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(int64_t));
-  return out;
-}
+int dr_probe_release(dr_probe* handle) { return g_probe_handles.release(handle); }
 
 int dr_state_scan_order(dr_state* state, int64_t** order, int64_t* n) {
   if (!state || !order || !n) return DR_E_INVALID_ARG;
   *order = nullptr;
   *n = 0;
-  return guard(state->ctx, [&] {
+  return guard_timed(state->ctx, [&] {
     HIP_OK(hipSetDevice(state->ctx->device));
     std::vector<int64_t> v = scan_order(*state);
     *order = malloc_copy(v);
@@ -7022,7 +6928,7 @@ int dr_state_partition_groups(dr_state* state, const int64_t* rows, int64_t nrow
   *order = nullptr;
   *group_off = nullptr;
   *ngroups = 0;
-  return guard(state->ctx, [&] {
+  return guard_timed(state->ctx, [&] {
     HIP_OK(hipSetDevice(state->ctx->device));
     std::vector<int64_t> o, g;
     partition_groups(*state, rows, nrows, o, g);
@@ -7037,7 +6943,7 @@ int dr_state_write_checkpoint(dr_state* state, int32_t part, int32_t parts, uint
   if (!state || !bytes || !len || parts < 1 || part < 1 || part > parts) return DR_E_INVALID_ARG;
   *bytes = nullptr;
   *len = 0;
-  return guard(state->ctx, [&] {
+  return guard_timed(state->ctx, [&] {
     HIP_OK(hipSetDevice(state->ctx->device));
     CkPartOut o;
     write_checkpoint_part(*state, part, parts, opts, row_group_rows, o);
@@ -7172,13 +7078,11 @@ int dr_shard_finish(dr_shard* shard, const uint8_t* verdict_back, dr_state** out
   if (!shard || !shard->st || !out || (shard->nsend && !verdict_back)) return DR_E_INVALID_ARG;
   *out = nullptr;
   dr_ctx* ctx = shard->ctx;
-  int rc = guard(ctx, [&] {
+  return guard_timed(ctx, [&] {
     if (!shard->reduced) fail(DR_E_INVALID_ARG, "dr_shard_finish before dr_shard_reduce");
     *out = shard_finish(*shard, verdict_back);
     ctx->collect_timings();
   });
-  if (rc != DR_OK) ctx->drop_timings();
-  return rc;
 }
 
 int dr_parse_commits(dr_ctx* ctx, const dr_staged* staged, dr_parsed** out, dr_lines* lines) {
